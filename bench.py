@@ -11,7 +11,11 @@ inside the timed region; at N = 1 the same call over a world-1 communicator. tor
 all-reduce of the step time. The scene is built and uploaded, and the tile order's cost pass
 run, before timing; the cost pass's time is amortised into `value` (value_steady without).
 
-Prints ONE JSON line (rank 0). Besides the contract fields it carries
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs
+(--dump-outputs DIR: the last timed step's frame as DIR/frame.npy) and the JSON line. The
+roofline, the count pass, the CPU baseline and the parity check below run under --full.
+
+Prints ONE JSON line (rank 0). Besides the contract fields it carries, under --full,
   roofline:     the binding resource, VALU issue: the issue cycles the launch's VALU
                 instruction mix needs (per-class counts from a rocprofv3 PMC pass of THIS
                 build and workload, profiles/pmc.json keyed by the source hash; cycles
@@ -70,12 +74,19 @@ def parse():
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--depth", type=int, default=None)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also price the roofline (the PMC record of this build), run the "
+                         "count_work pass, the CPU baseline and the parity check against the oracle; a plain run "
+                         "leaves those fields null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to its caller, the f64 frame (rank 0), as "
+                         "DIR/frame.npy; a frame over 60 MB as a fixed seeded sample of its pixels")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--t10-seconds", type=float, default=10.0, help="CPU time of the reference 10-thread split run")
     ap.add_argument("--count-spp", type=int, default=16, help="spp of the untimed count_work pass")
     ap.add_argument("--spp-chunk", type=int, default=0, help="samples per chunk (0: the library's automatic choice)")
-    ap.add_argument("--no-count", action="store_true", help="skip the count_work pass (profiling runs)")
+    ap.add_argument("--no-count", action="store_true", help="--full without the count_work pass")
     ap.add_argument("--ppm", default="", help="write the rendered frame (rank 0) as a P3 PPM")
     ap.add_argument("--frame-npy", default="", help="save the rendered f64 frame (rank 0) as .npy")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "gloo", "none"],
@@ -207,6 +218,22 @@ def valu_issue_cycles(counts, calib, other=None, isa=None, bound=0):
         need += n * by_counter.get(key[len("SQ_INSTS_VALU_"):], cyc[cls])
     need += max(0.0, total - known) * cyc["other"]
     return need
+
+
+DUMP_MAX_BYTES = 60 * 10**6    # of array data: the file stays under 64 MB, decimal or binary
+
+
+def dump_outputs(dirname, frame):
+    """--dump-outputs: the frame (H, W, 3), f64, as DIR/frame.npy. A frame over 60 MB (C5) is
+    written as (n, 3): the n pixels, in raster order, of a sample drawn without replacement by a
+    fixed seed — the same pixels in every run of the same geometry."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    if frame.nbytes > DUMP_MAX_BYTES:
+        px = frame.reshape(-1, frame.shape[-1])
+        n = DUMP_MAX_BYTES // (px.shape[1] * px.itemsize)
+        frame = px[np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))]
+    np.save(os.path.join(dirname, "frame.npy"), np.ascontiguousarray(frame, dtype=np.float64))
 
 
 class stdout_to_stderr:
@@ -442,6 +469,11 @@ def main():
         dist.all_gather(allr, mine)
         per_rank = [{"rank": r, "kernel_ms": round(float(v[0]), 3), "gather_ms": round(float(v[1]), 3),
                      "render_ms": round(float(v[2]), 3), "samples": int(v[3])} for r, v in enumerate(allr)]
+    # the frame of the last timed step, f64 mean radiance, row 0 = bottom (copied only when asked for)
+    need_frame = rank == 0 and (args.dump_outputs or args.ppm or args.frame_npy or args.full)
+    frame_np = frame.cpu().numpy() if need_frame else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame_np)
     last = renderer.stats()
     direct = comm is not None and comm.stats().slab_bytes == 0   # the world-1 direct render (RT_OPT_COMM_DIRECT)
 
@@ -454,17 +486,19 @@ def main():
     k_ms = float(np.mean(kernel_ms)) if kernel_ms else float("nan")
     step_ms = [(b - a) * 1e3 for a, b in zip([t0] + step_ends[:-1], step_ends)]
 
-    # ---- roofline: VALU issue (the binding resource), from the PMC pass of this build. The build
+    # ---- roofline (--full): VALU issue (the binding resource), from the PMC pass of this build. The build
     # is the LOADED library's (rt_build_info, compiled in from __graft_entry__.source_hash()); a
     # library that does not match the sources next to it is a stale build, and no PMC record is
     # quoted for it
     src_hash = rt.build_info()
-    tree_hash = ge.source_hash()
+    tree_hash = ge.source_hash() if args.full else src_hash
     workload = [args.scene, W, H, spp, depth, world, last.schedule] + ([1] if f32 else [])
-    pmc, calib = pmc_entry(src_hash, workload) if src_hash == tree_hash else (None, None)
+    pmc, calib = pmc_entry(src_hash, workload) if args.full and src_hash == tree_hash else (None, None)
     roofline = {"bound": "valu", "achieved": None, "peak": None, "unit": "G SIMD-cycles/s", "frac": None,
                 "traffic": None, "src_hash": src_hash, "src_hash_from": "rt_build_info (the loaded library)"}
-    if src_hash != tree_hash:
+    if not args.full:
+        roofline["note"] = "not priced in a plain run (bench.py --full)"
+    elif src_hash != tree_hash:
         roofline["note"] = ("stale library: built from sources %s, the tree is %s; no PMC record quoted"
                             % (src_hash, tree_hash))
     elif pmc is not None and calib is not None:
@@ -515,7 +549,7 @@ def main():
     # ---- SURVEY §8(d) algorithmic bytes per sample (LDS/L1/L2-served; not an HBM figure)
     count_spp = min(args.count_spp, spp)
     cs = None
-    if not args.no_count and not f32:   # count_work is an f64-mode diagnostic
+    if args.full and not args.no_count and not f32:   # count_work is an f64-mode diagnostic
         cp = rt.Renderer.params(W, H, count_spp, depth, bg, args.seed, row_begin=rank, row_stride=world,
                                 row_block=1 if tiles else ROW_BLOCK, tile_shard=int(tiles),
                                 spp_chunk=min(args.spp_chunk, count_spp), out_format=rt.RT_OUT_F32, count_work=1)
@@ -534,16 +568,15 @@ def main():
                "node_lane_occupancy": round(cs.node_visits / max(64 * cs.wave_node_steps, 1), 3),
                "leaf_lane_occupancy": round(cs.prim_tests / max(64 * cs.wave_leaf_steps, 1), 3)}
 
-    frame_np = frame.cpu().numpy() if rank == 0 else None   # f64 mean radiance, row 0 = bottom
     if args.ppm and rank == 0:
         rt.write_ppm(frame_np, args.ppm)   # f64: rt_write_ppm_f64, the reference's bytes
     if args.frame_npy and rank == 0:
         np.save(args.frame_npy, frame_np)
 
-    progress("timed steps done; count pass, CPU baseline and parity")
-    # ---- CPU baseline + parity (rank 0, N = 1 only)
+    # ---- CPU baseline + parity (--full; rank 0, N = 1 only)
     cpu, parity = None, None
-    if rank == 0 and not dist_on and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not dist_on and not args.no_cpu_baseline:
+        progress("timed steps done; CPU baseline and parity")
         from tests import oracle_binding as ob
         cores, n_aff, quota = usable_cores()
         # calibrate on `cores` interleaved rows at low spp, then take an interleaved subset of the

@@ -7,9 +7,9 @@
 #   STEP is a preset name below, or a raw "<seconds>:<name>:<command>" spec.
 #   tests            pytest -m gpu (the driver's GPU tier)
 #   smoke            __graft_entry__.smoke()
-#   bench            bench.py with no arguments (the driver's bench line)
-#   bench_c1..c5     bench.py --config Cn (f64)
-#   f32_c2..c4       bench.py --config Cn --precision f32
+#   bench            bench.py --full (the headline with roofline, CPU baseline and parity)
+#   bench_c1..c5     bench.py --full --config Cn (f64)
+#   f32_c2..c4       bench.py --config Cn --precision f32 (plain: the timed steps alone)
 #   prof_c1..c5      scripts/profile_r02.sh on that config (kernel trace + PMC passes)
 #   calib            scripts/calib_r02.sh (VALU issue-rate calibration through rocprofv3)
 # env: PREFIX (log-name prefix, e.g. r03a_). Round 3 sessions: scripts/sessions_r03.sh
@@ -21,12 +21,12 @@ for s in "$@"; do
     case "$s" in
     tests) specs+=("900:${P}gpu_tests:python -u -m pytest tests -m gpu -v --maxfail=8 --timeout 300 --timeout-method thread") ;;
     smoke) specs+=("300:${P}smoke:python -c 'import __graft_entry__ as g; g.smoke()'") ;;
-    bench) specs+=("600:${P}bench_default:python bench.py") ;;
-    bench_c1) specs+=("300:${P}bench_c1:python bench.py --config C1 --steps 20 --warmup 3") ;;
-    bench_c2) specs+=("300:${P}bench_c2:python bench.py --steps 10 --warmup 2") ;;
-    bench_c3) specs+=("300:${P}bench_c3:python bench.py --config C3 --steps 5 --warmup 1") ;;
-    bench_c4) specs+=("400:${P}bench_c4:python bench.py --config C4 --steps 3 --warmup 1") ;;
-    bench_c5) specs+=("600:${P}bench_c5:python bench.py --config C5 --steps 3 --warmup 1") ;;
+    bench) specs+=("600:${P}bench_default:python bench.py --full") ;;
+    bench_c1) specs+=("300:${P}bench_c1:python bench.py --full --config C1 --steps 20 --warmup 3") ;;
+    bench_c2) specs+=("300:${P}bench_c2:python bench.py --full --steps 10 --warmup 2") ;;
+    bench_c3) specs+=("300:${P}bench_c3:python bench.py --full --config C3 --steps 5 --warmup 1") ;;
+    bench_c4) specs+=("400:${P}bench_c4:python bench.py --full --config C4 --steps 3 --warmup 1") ;;
+    bench_c5) specs+=("600:${P}bench_c5:python bench.py --full --config C5 --steps 3 --warmup 1") ;;
     f32_c2) specs+=("300:${P}f32_c2:python bench.py --steps 10 --warmup 2 --precision f32 $NB") ;;
     f32_c3) specs+=("300:${P}f32_c3:python bench.py --config C3 --steps 5 --warmup 1 --precision f32 $NB") ;;
     f32_c4) specs+=("300:${P}f32_c4:python bench.py --config C4 --steps 3 --warmup 1 --precision f32 $NB") ;;

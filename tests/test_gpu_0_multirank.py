@@ -48,14 +48,15 @@ def _run_ranks(world, scene, W, H, spp, out, block=1):
     return rcs
 
 
-def _bench(tmp_path, world, tag, extra=(), rccl=False):
+def _bench(tmp_path, world, tag, extra=(), rccl=False, skip=("--no-cpu-baseline", "--no-count")):
     """bench.py as child processes (N > 1: torch.distributed.run, one child per rank), a
     small random-scene workload; returns (JSON line of rank 0, frame, PPM bytes). rccl: one
     rank under torch.distributed.run with --force-dist and the default transport (the library's
-    RCCL communicator, the unique id broadcast over torch's gloo control plane)."""
+    RCCL communicator, the unique id broadcast over torch's gloo control plane). skip: the legs of
+    --full these runs leave out (they have no effect on a plain run)."""
     frame, ppm = str(tmp_path / f"{tag}.npy"), str(tmp_path / f"{tag}.ppm")
     args = ["bench.py", "--gpus", str(world), "--device", "0", "--scene", "0", "--width", "160", "--height", "90",
-            "--spp", "8", "--depth", "50", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-count",
+            "--spp", "8", "--depth", "50", "--steps", "2", "--warmup", "1", *skip,
             "--frame-npy", frame, "--ppm", ppm, *extra]
     if rccl:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
@@ -146,6 +147,28 @@ def test_bench_py_rccl_branch_at_world_size_1(tmp_path):
     assert fd.dtype == np.float64 and fd.shape == f1.shape == fs.shape == fn.shape == (90, 160, 3)
     assert np.array_equal(fd, f1) and np.array_equal(fs, f1) and np.array_equal(fn, f1)
     assert pd == p1 == ps == pn
+
+
+@pytest.mark.timeout(900)
+def test_bench_py_full_and_dump_outputs(tmp_path):
+    """A plain run times its steps and leaves the roofline, the count pass, the CPU baseline and the
+    parity check to --full; --dump-outputs DIR writes the last timed step's frame as DIR/frame.npy
+    (f64, the array --frame-npy saves), the same in both runs."""
+    dp, df = tmp_path / "dump_plain", tmp_path / "dump_full"
+    jp, fp, _ = _bench(tmp_path, 1, "plain", extra=("--dump-outputs", str(dp)), skip=())
+    jf, ff, _ = _bench(tmp_path, 1, "full", extra=("--full", "--dump-outputs", str(df), "--cpu-seconds", "0.2",
+                                                   "--t10-seconds", "0.2"), skip=())
+    assert jp["cpu_baseline"] is None and jp["parity"] is None and jp["roofline"]["frac"] is None
+    assert jp["detail"]["algorithmic_bytes_survey_8d"] is None and "--full" in jp["roofline"]["note"]
+    assert jp["steps"] == 2 and len(jp["detail"]["kernel_ms_steps"]) == 2 and jp["ms_per_step"] > 0
+    assert jf["cpu_baseline"]["value"] > 0 and jf["parity"]["pass"] and jf["parity"]["linf"] <= 1e-3
+    assert jf["detail"]["algorithmic_bytes_survey_8d"]["casts_per_sample"] >= 1
+    assert "--full" not in jf["roofline"].get("note", "") and jf["roofline"]["src_hash"] == jp["roofline"]["src_hash"]
+    for d, f in ((dp, fp), (df, ff)):
+        assert sorted(os.listdir(d)) == ["frame.npy"]
+        a = np.load(d / "frame.npy")
+        assert a.dtype == np.float64 and a.shape == (90, 160, 3) and np.array_equal(a, f)
+    assert np.array_equal(fp, ff)
 
 
 @pytest.mark.timeout(900)
