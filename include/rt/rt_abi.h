@@ -26,6 +26,8 @@
  *   rt_comm_* /               the partition of one frame over workers (main.rs:497-551)
  *   rt_render_gather          and the merge of their buffers (main.rs:542-547), over GPUs:
  *                             8x8 tile shards, one RCCL gather to rank 0, a reorder kernel
+ *   rt_render_adaptive        (new) the same driver loop with the per-pixel sample count
+ *                             (main.rs:516) decided per 8x8 tile from the estimate's noise
  *
  * Threading: a context is bound to one device and is used by one host thread at
  * a time. Worlds are plain host objects.
@@ -394,6 +396,82 @@ typedef int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_
  * progress after each batch; out as rt_render (sums / samples done if stopped early). */
 int rt_render_progressive(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, int batch_spp,
                           rt_progress_fn progress, void* user, void* out);
+
+/* ---- tile-adaptive sampling (additive to ABI v6: new symbols only, RT_ABI_VERSION stays 6) ----
+ * Every other render path spends p->spp samples on every pixel. rt_render_adaptive samples the
+ * frame in passes and, after each pass, stops the 8x8 tiles whose estimate has converged; it also
+ * hands back the per-tile sample counts and a per-pixel noise estimate. Every draw is keyed by
+ * (pixel, sample), so a tile that stopped at n samples holds exactly rt_render's pixels at spp = n
+ * (same spp_chunk), bit for bit.
+ *
+ * The criterion. Per pixel, after its tile has n >= 2 samples:
+ *   S      the RGB sum of its samples
+ *   Y(c)   = 0.2126 r + 0.7152 g + 0.0722 b, in f64, evaluated left to right, no contraction
+ *   Q      = sum over samples j of Y(sample_j)^2
+ *   Ys     = Y(S),  m = Ys / n
+ *   var    = max(0, (Q - Ys Ys / n) / (n - 1))
+ *   se     = sqrt(var / n)                 the standard error of the luminance mean
+ *   e_px   = se / sqrt(max(m, 1e-4))       the error after the output's sqrt gamma, up to the factor 1/2
+ * Per tile: E_t = the mean of e_px over the tile's pixels inside the image (an edge tile counts
+ * only those).
+ * Stop rule, after every pass: a tile stops when E_t <= threshold or its count has reached p->spp
+ * (the maximum); a stopped tile is never re-activated. threshold <= 0 never stops early; +inf
+ * stops every tile at min_spp.
+ * Sample counts: every tile gets min_spp samples first, active tiles then step_spp more per pass,
+ * both rounded up to a multiple of the chunk (p->spp_chunk, or rt_render's automatic chunk for
+ * p->spp, as rt_render_progressive); the last pass is cut at p->spp. All active tiles therefore
+ * share one sample count, and a pass is one sample range [done, done + step).
+ * Sum order: the RGB sums follow rt_render's (chunk sums from 0.0 in sample order, added in chunk
+ * order); Q uses the same association.
+ *
+ * Each pass renders the active tiles as one tile shard under a tile order private to the call
+ * ([stopped tiles | active tiles]; the context's own order, rt_ctx_set_tile_order, is not touched)
+ * on the POOL schedule's per-sample buffer, whatever the context is set to; buffer batches
+ * (RT_OPT_TRACE_BUF_BYTES) carry the sums across. A moments kernel reduces the records into
+ * frame-layout S and Q and the per-tile error, and a compact kernel re-deals the tiles.
+ * p: the shard fields (row_begin, row_stride other than 0 / 1, row_block > 1, tile_shard) must be
+ * unset (RT_ERR_INVALID); count_work is ignored; p->spp >= 2. RT_PREC_F32 contexts:
+ * RT_ERR_UNSUPPORTED. One GPU. */
+typedef struct rt_adaptive_params {
+    int32_t min_spp;     /* >= 2: samples every tile gets before the first test (rounded up to the chunk) */
+    int32_t step_spp;    /* >= 1: samples per later pass (rounded up to the chunk) */
+    double threshold;    /* on E_t; <= 0: never stop early */
+} rt_adaptive_params;
+
+/* Host pointers, or device pointers if p->out_on_device. Tiles in raster order: ceil(width/8) per
+ * tile row, t = ty * ceil(width/8) + tx, rows from the bottom as the frame's. */
+typedef struct rt_adaptive_out {
+    void* mean;            /* required: height x width x 3 of p->out_format, S * (1 / the tile's count) */
+    uint32_t* tile_spp;    /* optional: samples per pixel each tile got */
+    double* tile_error;    /* optional: E_t at the tile's last pass */
+    double* stderr_map;    /* optional: height x width, se per pixel */
+} rt_adaptive_out;
+
+/* Synchronous, whether the outputs are host or device memory. */
+int rt_render_adaptive(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, const rt_adaptive_params* ap,
+                       const rt_adaptive_out* out);
+
+typedef struct rt_adaptive_stats {
+    int32_t passes;             /* passes of the last rt_render_adaptive */
+    int32_t min_spp, step_spp;  /* as rounded to the chunk (min_spp at most p->spp) */
+    int32_t spp_chunk;
+    int32_t tiles;              /* tiles of the frame */
+    int32_t max_pass_batches;   /* the most buffer batches one pass took */
+    uint64_t samples_traced;    /* 64 x the sum of tile_spp over all tiles: an edge tile's pixels past the
+                                   image are traced with it, as in every tile shard */
+    uint64_t samples_uniform;   /* width x height x p->spp: what rt_render traces for the frame */
+    double trace_ms;            /* HIP events, summed over passes: the trace kernels, */
+    double moments_ms;          /*   the moments reductions, */
+    double classify_ms;         /*   the compact launches (with their readback) */
+} rt_adaptive_stats;
+int rt_adaptive_last_stats(rt_ctx* ctx, rt_adaptive_stats* out);
+
+/* The criterion above on the host, no device needed: sums (height x width x 3) and q (height x
+ * width) are a frame's S and Q, tile_spp its per-tile sample counts (every one >= 2, else
+ * RT_ERR_INVALID); writes E_t per raster tile to tile_error_out and se per pixel to stderr_out
+ * (either may be NULL). For callers with accumulators of their own, and for tests. */
+int rt_adaptive_tile_errors_host(const double* sums, const double* q, const uint32_t* tile_spp, int width,
+                                 int height, double* tile_error_out, double* stderr_out);
 
 /* ---- output ------------------------------------------------------------------------------ */
 /* P3 PPM byte for byte as the reference writes it (write_color, math.rs:119-132; main.rs:472,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "rt/rt_abi.h"
+#include "adaptive_criterion.hpp"
 #include "ctx_internal.hpp"
 #include "scene_model.hpp"
 #include "trace_kernel.hpp"
@@ -102,6 +103,7 @@ struct rt_ctx {
     bool pending_stats = false;
     bool pending_counts = false;
     rt_stats stats{};
+    rt_adaptive_stats astats{};         // the last rt_render_adaptive (rt_adaptive_last_stats)
     uint32_t features = rtk::FEAT_ALL;  // of the uploaded scene
     int n_materials = 0, n_textures = 0;
     int block_chunks = 0;               // RT_OPT_BLOCK_CHUNKS: chunks per item-pool work block (0: auto)
@@ -1225,6 +1227,12 @@ struct Sink {
     void* out = nullptr;
     bool f64 = true;
     double scale = 1.0;
+    // rt_render_adaptive's passes (acc and out unused): a tile shard under the call's own tile
+    // order (moments->order), on the per-sample buffer whatever the context's schedule, reduced by
+    // the moments kernel into the call's frame-layout accumulators; n_done = samples per pixel
+    // of the shard's tiles once this range is in
+    const rtk::AdaptiveFrame* moments = nullptr;
+    int n_done = 0;
 };
 
 // Traces samples [s_begin, s_end) of the shard in chunks of `chunk` and reduces them into
@@ -1289,7 +1297,9 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
         K.tile_div_magic = (d >= 2 && m < ((uint64_t)1 << 32) && (uint64_t)img_tiles * e < ((uint64_t)1 << 32))
                                ? (uint32_t)m : 0u;
     }
-    if (p->tile_shard && c->tile_order_n > 0) {   // the context's tile order: every tile shard takes it
+    if (sink.moments) {   // the adaptive call's own order, dealt as a frame is (the order carries no cost ranking)
+        K.tile_order = sink.moments->order;
+    } else if (p->tile_shard && c->tile_order_n > 0) {   // the context's tile order: every tile shard takes it
         if (c->tile_order_n != img_tiles)
             return fail(RT_ERR_INVALID, "the tile order has " + std::to_string(c->tile_order_n) + " tiles, the frame " +
                                             std::to_string(img_tiles));
@@ -1313,6 +1323,7 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
     o.lds_stack = c->opt_lds && c->S.stack_entries <= kMaxLdsStack;
     o.count = count;
     o.f32 = c->opt_precision == RT_PREC_F32;
+    if (sink.moments && o.f32) return fail(RT_ERR_UNSUPPORTED, "adaptive sampling in the f32 mode");
     if (o.f32 && count && rtk::variant_features(o.features) != rtk::FEAT_SET_SPHERES &&
         rtk::variant_features(o.features) != rtk::FEAT_SET_FINAL)
         return fail(RT_ERR_UNSUPPORTED, "count_work in the f32 mode: the spheres and final-scene variants only");
@@ -1414,12 +1425,13 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
         // (the media variant, Cornell smoke 600x600x200: items 31.72 ms, per-sample buffer 30.28: pool)
         const bool cornell = variant == rtk::FEAT_SET_RECTINST;
         const bool fits_one = (size_t)total * sample_bytes <= buf_cap;
-        o.pool = c->opt_pool != RT_SCHED_AUTO ? c->opt_pool
+        o.pool = sink.moments                 ? RT_SCHED_POOL
+                 : c->opt_pool != RT_SCHED_AUTO ? c->opt_pool
                  : cornell && !o.f32 ? RT_SCHED_ITEMS
                  : (ring_ok || (size_t)total * sample_bytes <= 4 * buf_cap ? RT_SCHED_POOL : RT_SCHED_ITEMS);
         // POOL with the in-kernel reduction: chunk partials like ITEMS (the ring takes its share of
         // the bound first, the partials at least one chunk)
-        ring = o.pool == RT_SCHED_POOL && ring_ok && (c->opt_ring == 2 || !fits_one);
+        ring = o.pool == RT_SCHED_POOL && ring_ok && (c->opt_ring == 2 || !fits_one) && !sink.moments;
         // overlapped batches trace two launches at once, a ring each: a render that does not fit
         // one batch beside one ring budgets two
         size_t out_cap = buf_cap;
@@ -1456,7 +1468,8 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
         own_acc = false;
         bool oom = false;
         int rc = RT_OK;
-        if (per_sample && (n_batches > 1 || acc)) {  // acc_tmp = [open chunk sums | running total (no acc sink)]
+        // (an adaptive pass keeps its sums and the open chunk in the call's frame-layout accumulators)
+        if (per_sample && !sink.moments && (n_batches > 1 || acc)) {  // acc_tmp = [open chunk sums | running total (no acc sink)]
             rc = grow(c, stream, c->acc_tmp, c->acc_tmp_cap, 2 * px_bytes);
             if (rc) return rc;
             open = c->acc_tmp;
@@ -1543,7 +1556,11 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
             HIP_TRY(hipEventRecord(c->ev_tr[h], ts));
             HIP_TRY(hipStreamWaitEvent(stream, c->ev_tr[h], 0));
         }
-        if (!per_sample) {
+        if (sink.moments) {
+            HIP_TRY(rtk::launch_adaptive_moments(buf, *sink.moments, K.tiles_x, b1 - b0, chunk,
+                                                 (int)(((long long)b0 - s_begin) % chunk), bi == n_batches - 1,
+                                                 sink.n_done, stream));
+        } else if (!per_sample) {
             if (acc) HIP_TRY(rtk::launch_accumulate(buf, acc, n_px, K.n_chunks, stream));
             else HIP_TRY(rtk::launch_reduce(buf, sink.out, sink.f64, n_px, K.n_chunks, sink.scale, stream));
         } else if (!open) {
@@ -1834,6 +1851,197 @@ int rt_render_progressive(rt_ctx* c, const rt_camera* cam, const rt_render_param
     }
     rt_accum_destroy(a);
     return rc;
+}
+
+// ---- tile-adaptive sampling (rt_abi.h: the criterion; adaptive_kernel.hip: the kernels) ----------
+int rt_adaptive_tile_errors_host(const double* sums, const double* q, const uint32_t* tile_spp, int width,
+                                 int height, double* tile_error_out, double* stderr_out)
+{
+    if (!sums || !q || !tile_spp) return fail(RT_ERR_INVALID, "null argument");
+    if (width < 1 || height < 1 || (long long)width * height > 0xffffffffLL) return fail(RT_ERR_INVALID, "bad frame size");
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    for (long long t = 0; t < (long long)tiles_x * tiles_y; ++t)
+        if (tile_spp[t] < 2) return fail(RT_ERR_INVALID, "a tile with fewer than 2 samples has no variance estimate");
+    for (int ty = 0; ty < tiles_y; ++ty) {
+        for (int tx = 0; tx < tiles_x; ++tx) {
+            const size_t t = (size_t)ty * tiles_x + tx;
+            const double n = (double)tile_spp[t];
+            const int cw = std::min(8, width - tx * 8), ch = std::min(8, height - ty * 8);
+            double e = 0.0;
+            for (int k = 0; k < ch; ++k) {
+                for (int i = 0; i < cw; ++i) {
+                    const size_t px = (size_t)(ty * 8 + k) * width + (size_t)(tx * 8 + i);
+                    const rtk::PixelNoise pn = rtk::adaptive_pixel_noise(sums[3 * px], sums[3 * px + 1], sums[3 * px + 2],
+                                                                         q[px], n);
+                    e = e + pn.e;
+                    if (stderr_out) stderr_out[px] = pn.se;
+                }
+            }
+            if (tile_error_out) tile_error_out[t] = e / (double)(cw * ch);
+        }
+    }
+    return RT_OK;
+}
+
+namespace {
+struct DeviceBlock {   // one allocation for a call's device state, freed on every way out
+    void* p = nullptr;
+    ~DeviceBlock() { (void)hipFree(p); }
+};
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+}  // namespace
+
+int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_adaptive_params* ap,
+                       const rt_adaptive_out* out)
+{
+    if (!c || !cam || !p || !ap || !out || !out->mean) return fail(RT_ERR_INVALID, "null argument");
+    if (!c->has_scene) return fail(RT_ERR_NO_SCENE, "no scene uploaded");
+    if (p->row_begin != 0 || (p->row_stride != 0 && p->row_stride != 1) || p->row_block < 0 || p->row_block > 1 ||
+        p->tile_shard != 0)
+        return fail(RT_ERR_INVALID, "rt_render_adaptive renders whole frames: the shard fields must be unset");
+    // a pass: the tail of the call's tile order as one tile shard
+    rt_render_params rp = *p;
+    rp.row_stride = 1;
+    rp.row_block = 0;
+    rp.tile_shard = 1;
+    rp.count_work = 0;
+    if (bad_geometry(&rp) || p->spp < 2 || p->max_depth < 0 || (p->out_format != RT_OUT_F32 && p->out_format != RT_OUT_F64))
+        return fail(RT_ERR_INVALID, "bad render params (adaptive sampling needs spp >= 2)");
+    if (ap->min_spp < 2 || ap->step_spp < 1 || std::isnan(ap->threshold))
+        return fail(RT_ERR_INVALID, "bad adaptive params (min_spp >= 2, step_spp >= 1, threshold not NaN)");
+    if (c->opt_precision == RT_PREC_F32) return fail(RT_ERR_UNSUPPORTED, "adaptive sampling in the f32 mode");
+    const int W = p->width, H = p->height, tiles_x = (W + 7) / 8;
+    const long long tiles_ll = (long long)tiles_x * ((H + 7) / 8);
+    if (tiles_ll > 0x3fffffffLL) return fail(RT_ERR_INVALID, "too many tiles");
+    const int n_tiles = (int)tiles_ll;
+    const int chunk = p->spp_chunk > 0 ? std::min(p->spp_chunk, p->spp) : auto_chunk(p->spp);
+    auto rounded = [&](int v) { return (int)std::min<long long>(p->spp, ((long long)v + chunk - 1) / chunk * chunk); };
+    const int min_r = rounded(ap->min_spp), step_r = rounded(ap->step_spp);
+    const bool on_dev = p->out_on_device != 0;
+
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = p->stream ? (hipStream_t)p->stream : c->stream;
+    StreamScope scope(c, stream);
+    int rc = scope.begin();
+    if (rc) return rc;
+
+    // device state: [sum | sum_open | q | q_open | tile_error | se map (host-bound only)] f64, then
+    // [tile_spp | order A | order B | counts] u32; zeroed: the sums start from 0.0
+    const size_t hw = (size_t)W * (size_t)H, nt = (size_t)n_tiles;
+    const bool own_se = out->stderr_map && !on_dev;
+    const size_t n_f64 = 8 * hw + nt + (own_se ? hw : 0), n_u32 = 3 * nt + 2;
+    DeviceBlock blk;
+    HIP_TRY(hipMalloc(&blk.p, n_f64 * sizeof(double) + n_u32 * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(blk.p, 0, n_f64 * sizeof(double) + n_u32 * sizeof(uint32_t), stream));
+    double* d = (double*)blk.p;
+    rtk::AdaptiveFrame F{};
+    F.sum = d;
+    F.sum_open = d + 3 * hw;
+    F.q = d + 6 * hw;
+    F.q_open = d + 7 * hw;
+    F.tile_error = d + 8 * hw;
+    double* se_dev = out->stderr_map ? (on_dev ? out->stderr_map : d + 8 * hw + nt) : nullptr;
+    uint32_t* u = (uint32_t*)(d + n_f64);
+    F.tile_spp = u;
+    uint32_t* order[2] = {u + nt, u + 2 * nt};
+    uint32_t* counts = u + 3 * nt;
+    F.width = W;
+    F.height = H;
+    F.tiles_x = tiles_x;
+    {
+        std::vector<uint32_t> raster(nt);
+        for (size_t i = 0; i < nt; ++i) raster[i] = (uint32_t)i;
+        HIP_TRY(hipMemcpyAsync(order[0], raster.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));   // (raster is read until the copy is done)
+    }
+    EventPair ev;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+
+    rt_adaptive_stats as{};
+    as.min_spp = min_r;
+    as.step_spp = step_r;
+    as.spp_chunk = chunk;
+    as.tiles = n_tiles;
+    as.samples_uniform = (uint64_t)hw * (uint64_t)p->spp;
+    int done = 0, n_stopped = 0, cur = 0, batches = 0;
+    while (n_stopped < n_tiles && done < p->spp) {
+        const int end = std::min(p->spp, done + (done == 0 ? min_r : step_r));
+        rp.row_begin = n_stopped;
+        F.order = order[cur];
+        F.pos_begin = n_stopped;
+        Sink sink;
+        sink.moments = &F;
+        sink.n_done = end;
+        rc = run_range(c, cam, &rp, done, end, chunk, stream, sink);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(ev.a, stream));
+        HIP_TRY(rtk::launch_adaptive_compact(order[cur], order[cur ^ 1], F.tile_error, n_tiles, n_stopped, ap->threshold,
+                                             end >= p->spp, counts, stream));
+        uint32_t h_counts[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(h_counts, counts, sizeof h_counts, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(ev.b, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float t_trace = 0, t_moments = 0, t_classify = 0;
+        HIP_TRY(hipEventElapsedTime(&t_trace, c->ev[0], c->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&t_moments, c->ev[1], c->ev[2]));
+        HIP_TRY(hipEventElapsedTime(&t_classify, ev.a, ev.b));
+        as.trace_ms += t_trace;
+        as.moments_ms += t_moments;
+        as.classify_ms += t_classify;
+        as.passes += 1;
+        as.max_pass_batches = std::max(as.max_pass_batches, c->stats.n_batches);
+        as.samples_traced += 64ull * (uint64_t)(n_tiles - n_stopped) * (uint64_t)(end - done);
+        batches += c->stats.n_batches;
+        if ((int)h_counts[0] < n_stopped || h_counts[0] + h_counts[1] != (uint32_t)n_tiles)
+            return fail(RT_ERR_HIP, "adaptive compact: inconsistent tile counts");
+        n_stopped = (int)h_counts[0];
+        cur ^= 1;
+        done = end;
+    }
+
+    const size_t mean_bytes = hw * 3 * (p->out_format == RT_OUT_F64 ? 8 : 4);
+    void* dev_mean = out->mean;
+    if (!on_dev) {
+        rc = out_staging(c, stream, mean_bytes, dev_mean);
+        if (rc) return rc;
+    }
+    HIP_TRY(rtk::launch_adaptive_resolve(F.sum, F.q, F.tile_spp, dev_mean, p->out_format == RT_OUT_F64, se_dev, W, H, stream));
+    const hipMemcpyKind kind = on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (!on_dev) HIP_TRY(hipMemcpyAsync(out->mean, dev_mean, mean_bytes, kind, stream));
+    if (own_se) HIP_TRY(hipMemcpyAsync(out->stderr_map, se_dev, hw * sizeof(double), kind, stream));
+    if (out->tile_spp) HIP_TRY(hipMemcpyAsync(out->tile_spp, F.tile_spp, nt * sizeof(uint32_t), kind, stream));
+    if (out->tile_error) HIP_TRY(hipMemcpyAsync(out->tile_error, F.tile_error, nt * sizeof(double), kind, stream));
+    rc = scope.end();
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
+
+    // rt_last_stats: the call as a whole (the variant fields are the last pass's)
+    c->stats.kernel_ms = as.trace_ms;
+    c->stats.reduce_ms = as.moments_ms;
+    c->stats.samples = as.samples_traced;
+    c->stats.n_batches = batches;
+    c->stats.n_chunks = (p->spp + chunk - 1) / chunk;
+    c->stats.n_items = 64ull * (uint64_t)n_tiles * (uint64_t)c->stats.n_chunks;
+    c->stats.casts = c->stats.node_visits = c->stats.prim_tests = 0;
+    c->pending_stats = false;
+    c->pending_counts = false;
+    c->astats = as;
+    return RT_OK;
+}
+
+int rt_adaptive_last_stats(rt_ctx* c, rt_adaptive_stats* out)
+{
+    if (!c || !out) return fail(RT_ERR_INVALID, "null argument");
+    *out = c->astats;
+    return RT_OK;
 }
 
 int rt_last_stats(rt_ctx* c, rt_stats* out)

@@ -1,0 +1,257 @@
+// adaptive_kernel.hip — the kernels of tile-adaptive sampling (rt_render_adaptive): the moments
+// reduction over a pass's per-sample records, the classify / compact step that re-deals the tiles
+// between passes, and the resolve. The criterion itself is adaptive_criterion.hpp.
+#include "adaptive_criterion.hpp"
+#include "trace_kernel.hpp"
+
+namespace rtk {
+
+// reduce_samples_carry's contract with a second moment, organised as reduce_samples_tiled: one
+// workgroup per tile of the shard, wave w of kMomentWaves sums chunk segments w, w + W, ... of
+// the tile's 64 pixels (four samples' loads in flight, each wave reading the tile's 64
+// consecutive records of a sample), parks the segment sums in LDS, and wave 0 adds a round's
+// segments in order to the running totals: rt_render's additions in rt_render's order.
+//
+// A batch holds samples [0, n_samples) of which the first continues a chunk `pos` samples in
+// (its sum so far in *_open); segment k covers the batch's samples of chunk k counted from that
+// chunk's start. A segment that reaches its chunk's end (or the pass's end, `close`) is added to
+// the closed totals; the last one otherwise goes back to *_open. Shard tile m is the raster tile
+// order[pos_begin + m], and the totals are in frame layout (row 0 = bottom, as rt_render's out).
+// On `close` wave 0 also evaluates the criterion with n_done samples per pixel, sums e_px over the
+// tile's in-image pixels across its 64 lanes and writes tile_error / tile_spp of the raster tile.
+constexpr int kMomentWaves = 8;
+__global__ void __launch_bounds__(64 * kMomentWaves) adaptive_moments(const double* __restrict__ samples,
+                                                                       AdaptiveFrame F, int n_samples, int chunk,
+                                                                       int pos, int close, int n_done)
+{
+    __shared__ double part[kMomentWaves][4][64];
+    const unsigned m = blockIdx.x;
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const unsigned t = F.order[(size_t)F.pos_begin + m];
+    const int tx = (int)(t % (unsigned)F.tiles_x), ty = (int)(t / (unsigned)F.tiles_x);
+    const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+    const bool inside = x < F.width && y < F.height;
+    const size_t px = inside ? (size_t)y * (size_t)F.width + (size_t)x : 0;
+    const double* base = samples + ((size_t)m * (size_t)n_samples * 64 + (size_t)lane) * 3;
+    const int n_seg = (n_samples + pos + chunk - 1) / chunk;
+    double r = 0.0, g = 0.0, b = 0.0, q = 0.0;          // wave 0: the closed chunks' totals
+    double o_r = 0.0, o_g = 0.0, o_b = 0.0, o_q = 0.0;  // wave 0: the chunk left open
+    if (w == 0 && inside) {
+        r = F.sum[3 * px + 0];
+        g = F.sum[3 * px + 1];
+        b = F.sum[3 * px + 2];
+        q = F.q[px];
+    }
+    for (int k0 = 0; k0 < n_seg; k0 += kMomentWaves) {
+        const int k = k0 + w;
+        if (k < n_seg) {
+            const int j0 = max(0, k * chunk - pos), j1 = min(n_samples, (k + 1) * chunk - pos);
+            double cr = 0.0, cg = 0.0, cb = 0.0, cq = 0.0;
+            if (k == 0 && pos > 0 && inside) {
+                cr = F.sum_open[3 * px + 0];
+                cg = F.sum_open[3 * px + 1];
+                cb = F.sum_open[3 * px + 2];
+                cq = F.q_open[px];
+            }
+            int j = j0;
+            for (; j + 4 <= j1; j += 4) {
+                double v[4][3];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double* p = base + (size_t)(j + i) * 192;
+                    v[i][0] = p[0];
+                    v[i][1] = p[1];
+                    v[i][2] = p[2];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double yl = adaptive_luma(v[i][0], v[i][1], v[i][2]);
+                    cr = cr + v[i][0];
+                    cg = cg + v[i][1];
+                    cb = cb + v[i][2];
+                    cq = cq + yl * yl;
+                }
+            }
+            for (; j < j1; ++j) {
+                const double* p = base + (size_t)j * 192;
+                const double v0 = p[0], v1 = p[1], v2 = p[2];
+                const double yl = adaptive_luma(v0, v1, v2);
+                cr = cr + v0;
+                cg = cg + v1;
+                cb = cb + v2;
+                cq = cq + yl * yl;
+            }
+            part[w][0][lane] = cr;
+            part[w][1][lane] = cg;
+            part[w][2][lane] = cb;
+            part[w][3][lane] = cq;
+        }
+        __syncthreads();
+        if (w == 0) {
+            const int nk = min(kMomentWaves, n_seg - k0);
+            for (int i = 0; i < nk; ++i) {
+                const bool closed = (k0 + i + 1) * chunk - pos <= n_samples || close;
+                if (closed) {
+                    r = r + part[i][0][lane];
+                    g = g + part[i][1][lane];
+                    b = b + part[i][2][lane];
+                    q = q + part[i][3][lane];
+                } else {   // the batch's last segment, its chunk continued by the next batch
+                    o_r = part[i][0][lane];
+                    o_g = part[i][1][lane];
+                    o_b = part[i][2][lane];
+                    o_q = part[i][3][lane];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (w != 0) return;
+    if (inside) {
+        F.sum[3 * px + 0] = r;
+        F.sum[3 * px + 1] = g;
+        F.sum[3 * px + 2] = b;
+        F.q[px] = q;
+        if (!close) {
+            F.sum_open[3 * px + 0] = o_r;
+            F.sum_open[3 * px + 1] = o_g;
+            F.sum_open[3 * px + 2] = o_b;
+            F.q_open[px] = o_q;
+        }
+    }
+    if (!close) return;
+    double e = inside ? adaptive_pixel_noise(r, g, b, q, (double)n_done).e : 0.0;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) e = e + __shfl_xor(e, d, 64);   // every lane: the same sum
+    if (lane == 0) {
+        const int cw = min(8, F.width - tx * 8), ch = min(8, F.height - ty * 8);
+        F.tile_error[t] = e / (double)(cw * ch);
+        F.tile_spp[t] = (uint32_t)n_done;
+    }
+}
+
+// One workgroup rewrites the tile order after a pass as [stopped tiles | active tiles]: positions
+// below n_stopped are copied, the active ones after them are split by the stop rule, each part in
+// its old order. Ranks come from ballots and popcounts within a wave and a prefix over the
+// workgroup's wave counts in LDS, so the new order is a function of the tile errors alone.
+// counts[0] = tiles stopped so far, counts[1] = tiles still active.
+constexpr int kCompactThreads = 1024;
+__global__ void __launch_bounds__(kCompactThreads) adaptive_compact(const uint32_t* __restrict__ order_in,
+                                                                    uint32_t* __restrict__ order_out,
+                                                                    const double* __restrict__ tile_error,
+                                                                    int n_tiles, int n_stopped, double threshold,
+                                                                    int at_max, uint32_t* __restrict__ counts)
+{
+    constexpr int kWaves = kCompactThreads / 64;
+    __shared__ unsigned w_stop[kWaves], w_keep[kWaves];
+    __shared__ unsigned total_stop;
+    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const unsigned long long below = lane ? ~0ULL >> (64 - lane) : 0ULL;   // the lanes before this one
+    for (int i = tid; i < n_stopped; i += kCompactThreads) order_out[i] = order_in[i];
+
+    // the tiles this pass stops
+    unsigned mine = 0;
+    for (int p0 = n_stopped; p0 < n_tiles; p0 += kCompactThreads) {
+        const int p = p0 + tid;
+        const bool stop = p < n_tiles && (at_max || (threshold > 0.0 && tile_error[order_in[p]] <= threshold));
+        mine += (unsigned)__popcll(__ballot(stop));
+    }
+    if (lane == 0) w_stop[w] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned s = 0;
+        for (int i = 0; i < kWaves; ++i) s += w_stop[i];
+        total_stop = s;
+    }
+    __syncthreads();
+    const unsigned new_stop = total_stop;
+
+    unsigned base_stop = (unsigned)n_stopped, base_keep = (unsigned)n_stopped + new_stop;
+    for (int p0 = n_stopped; p0 < n_tiles; p0 += kCompactThreads) {
+        const int p = p0 + tid;
+        const bool valid = p < n_tiles;
+        const unsigned tile = valid ? order_in[p] : 0u;
+        const bool stop = valid && (at_max || (threshold > 0.0 && tile_error[tile] <= threshold));
+        const unsigned long long bs = __ballot(stop), bk = __ballot(valid && !stop);
+        __syncthreads();   // the previous round's counts are read
+        if (lane == 0) {
+            w_stop[w] = (unsigned)__popcll(bs);
+            w_keep[w] = (unsigned)__popcll(bk);
+        }
+        __syncthreads();
+        unsigned before_stop = 0, before_keep = 0, round_stop = 0, round_keep = 0;
+        for (int i = 0; i < kWaves; ++i) {
+            if (i < w) {
+                before_stop += w_stop[i];
+                before_keep += w_keep[i];
+            }
+            round_stop += w_stop[i];
+            round_keep += w_keep[i];
+        }
+        if (stop) order_out[base_stop + before_stop + (unsigned)__popcll(bs & below)] = tile;
+        else if (valid) order_out[base_keep + before_keep + (unsigned)__popcll(bk & below)] = tile;
+        base_stop += round_stop;
+        base_keep += round_keep;
+    }
+    if (tid == 0) {
+        counts[0] = (unsigned)n_stopped + new_stop;
+        counts[1] = (unsigned)n_tiles - (unsigned)n_stopped - new_stop;
+    }
+}
+
+// mean = sum * (1 / the tile's sample count), as rt_render writes it, and (se_map not null) the
+// standard error of each pixel's luminance mean. One thread per pixel of the frame.
+template <typename T>
+__global__ void __launch_bounds__(256) adaptive_resolve(const double* __restrict__ sum, const double* __restrict__ q,
+                                                        const uint32_t* __restrict__ tile_spp, T* __restrict__ mean,
+                                                        double* __restrict__ se_map, int width, int height,
+                                                        int tiles_x)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)width * height) return;
+    const int y = (int)(i / width), x = (int)(i - (long long)y * width);
+    const double n = (double)tile_spp[(size_t)(y >> 3) * (size_t)tiles_x + (size_t)(x >> 3)];
+    const double scale = 1.0 / n;
+    const double r = sum[3 * i + 0], g = sum[3 * i + 1], b = sum[3 * i + 2];
+    mean[3 * i + 0] = (T)(r * scale);
+    mean[3 * i + 1] = (T)(g * scale);
+    mean[3 * i + 2] = (T)(b * scale);
+    if (se_map) se_map[i] = adaptive_pixel_noise(r, g, b, q[i], n).se;
+}
+
+hipError_t launch_adaptive_moments(const double* samples, const AdaptiveFrame& F, int n_tiles, int n_samples,
+                                   int chunk, int pos, bool close, int n_done, hipStream_t stream)
+{
+    if (n_tiles <= 0 || n_samples <= 0) return hipSuccess;
+    if (chunk < 1 || pos < 0 || pos >= chunk || n_done < 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(adaptive_moments, dim3((unsigned)n_tiles), dim3(64 * kMomentWaves), 0, stream, samples, F,
+                       n_samples, chunk, pos, (int)close, n_done);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_compact(const uint32_t* order_in, uint32_t* order_out, const double* tile_error,
+                                   int n_tiles, int n_stopped, double threshold, bool at_max, uint32_t* counts,
+                                   hipStream_t stream)
+{
+    if (n_tiles <= 0 || n_stopped < 0 || n_stopped > n_tiles) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(adaptive_compact, dim3(1), dim3(kCompactThreads), 0, stream, order_in, order_out, tile_error,
+                       n_tiles, n_stopped, threshold, (int)at_max, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_resolve(const double* sum, const double* q, const uint32_t* tile_spp, void* mean, bool f64,
+                                   double* se_map, int width, int height, hipStream_t stream)
+{
+    const long long blocks = ((long long)width * height + 255) / 256;
+    if (blocks <= 0) return hipSuccess;
+    const int tiles_x = (width + 7) / 8;
+    if (f64)
+        hipLaunchKernelGGL(adaptive_resolve<double>, dim3((unsigned)blocks), dim3(256), 0, stream, sum, q, tile_spp,
+                           (double*)mean, se_map, width, height, tiles_x);
+    else
+        hipLaunchKernelGGL(adaptive_resolve<float>, dim3((unsigned)blocks), dim3(256), 0, stream, sum, q, tile_spp,
+                           (float*)mean, se_map, width, height, tiles_x);
+    return hipGetLastError();
+}
+
+}  // namespace rtk

@@ -239,4 +239,31 @@ hipError_t launch_assemble_tiles(const void* gathered, void* frame, bool f64, in
 hipError_t launch_eval(int fn, const double* x, const double* y, const double* z, double* out, int n,
                        hipStream_t stream);
 
+// Tile-adaptive sampling (rt_render_adaptive; adaptive_kernel.hip). The frame-layout accumulators
+// of one call (row 0 = bottom, pixel y * width + x) and its tile order: the per-sample records of
+// shard tile m belong to the raster tile order[pos_begin + m].
+struct AdaptiveFrame {
+    double* sum;        // height x width x 3: RGB sums of the closed chunks
+    double* sum_open;   // height x width x 3: the chunk in progress between buffer batches
+    double* q;          // height x width: sum of squared sample luminances, closed chunks
+    double* q_open;     // height x width: the chunk in progress
+    double* tile_error; // per raster tile: E_t after the tile's last pass
+    uint32_t* tile_spp; // per raster tile: samples per pixel taken so far
+    const uint32_t* order;
+    int32_t width, height, tiles_x, pos_begin;
+};
+// a batch of n_samples records per pixel of the shard's n_tiles tiles (tiled_record order) added to
+// the frame's moments; pos = samples of the open chunk seen before this batch; close: the pass's
+// last batch (ends the chunk, writes tile_error / tile_spp = n_done for the shard's tiles)
+hipError_t launch_adaptive_moments(const double* samples, const AdaptiveFrame& F, int n_tiles, int n_samples,
+                                   int chunk, int pos, bool close, int n_done, hipStream_t stream);
+// order_out = [order_in's first n_stopped | the others that now stop | the others that go on];
+// a tile stops when at_max or (threshold > 0 and tile_error <= threshold); counts = {stopped, active}
+hipError_t launch_adaptive_compact(const uint32_t* order_in, uint32_t* order_out, const double* tile_error,
+                                   int n_tiles, int n_stopped, double threshold, bool at_max, uint32_t* counts,
+                                   hipStream_t stream);
+// mean (f32 / f64) = sum * (1 / tile_spp of the pixel's tile); se_map (may be null) = per-pixel se
+hipError_t launch_adaptive_resolve(const double* sum, const double* q, const uint32_t* tile_spp, void* mean, bool f64,
+                                   double* se_map, int width, int height, hipStream_t stream);
+
 }  // namespace rtk

@@ -78,6 +78,7 @@ EXPORTED = [
     "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_comm_rank",
     "rt_comm_tile_order", "rt_comm_tile_order_all", "rt_render_gather", "rt_render_gather_all",
     "rt_comm_last_stats", "rt_tiles_assemble", "rt_tiles_assemble_host", "rt_cost_tile_order",
+    "rt_render_adaptive", "rt_adaptive_last_stats", "rt_adaptive_tile_errors_host",
 ]
 
 # int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_total)
@@ -164,6 +165,28 @@ class CommStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AdaptiveParams(ctypes.Structure):
+    """rt_adaptive_params."""
+    _fields_ = [("min_spp", ctypes.c_int32), ("step_spp", ctypes.c_int32), ("threshold", ctypes.c_double)]
+
+
+class AdaptiveOut(ctypes.Structure):
+    """rt_adaptive_out: mean is required, the others may be null."""
+    _fields_ = [("mean", ctypes.c_void_p), ("tile_spp", ctypes.c_void_p), ("tile_error", ctypes.c_void_p),
+                ("stderr_map", ctypes.c_void_p)]
+
+
+class AdaptiveStats(ctypes.Structure):
+    """rt_adaptive_stats: the last rt_render_adaptive of a context."""
+    _fields_ = [("passes", ctypes.c_int32), ("min_spp", ctypes.c_int32), ("step_spp", ctypes.c_int32),
+                ("spp_chunk", ctypes.c_int32), ("tiles", ctypes.c_int32), ("max_pass_batches", ctypes.c_int32),
+                ("samples_traced", ctypes.c_uint64), ("samples_uniform", ctypes.c_uint64),
+                ("trace_ms", ctypes.c_double), ("moments_ms", ctypes.c_double), ("classify_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -233,6 +256,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_tiles_assemble": ([P, P, ctypes.c_int64, I, ctypes.POINTER(RenderParams), P], I),
         "rt_tiles_assemble_host": ([P, ctypes.c_int64, I, I, I, I, P, P], I),
         "rt_cost_tile_order": ([P, ctypes.c_int64, P], I),
+        "rt_render_adaptive": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
+                                ctypes.POINTER(AdaptiveParams), ctypes.POINTER(AdaptiveOut)], I),
+        "rt_adaptive_last_stats": ([P, ctypes.POINTER(AdaptiveStats)], I),
+        "rt_adaptive_tile_errors_host": ([P, P, P, I, I, P, P], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name, None)
@@ -530,6 +557,25 @@ def assemble_rows(slabs, height: int, world: int, out=None, row_block: int = 1):
     return out
 
 
+def adaptive_tile_errors_host(sums, q, tile_spp, width: int, height: int):
+    """rt_adaptive_tile_errors_host: the adaptive criterion (rt_abi.h) on the host, no device needed.
+    sums: height x width x 3 RGB sums, q: height x width sums of squared sample luminances,
+    tile_spp: samples per pixel of each raster 8x8 tile (all >= 2). Returns (tile_error per raster
+    tile, stderr_map height x width)."""
+    lib = load_library()
+    tiles = ((width + 7) // 8) * ((height + 7) // 8)
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    qq = np.ascontiguousarray(q, dtype=np.float64)
+    n = np.ascontiguousarray(np.asarray(tile_spp).reshape(-1), dtype=np.uint32)
+    if s.size != width * height * 3 or qq.size != width * height or n.size != tiles:
+        raise RTError(f"adaptive_tile_errors_host: {s.shape}, {qq.shape}, {n.shape} do not fit {width} x {height}")
+    err = np.empty(tiles, dtype=np.float64)
+    se = np.empty((height, width), dtype=np.float64)
+    _check(lib.rt_adaptive_tile_errors_host(s.ctypes.data, qq.ctypes.data, n.ctypes.data, width, height,
+                                            err.ctypes.data, se.ctypes.data), "rt_adaptive_tile_errors_host")
+    return err, se
+
+
 def write_ppm(rgb: np.ndarray, path: str, samples_per_pixel: int = 1) -> None:
     """P3 writer of the reference (write_color, math.rs:119-132; main.rs:472, 591-596):
     height x width x 3, row 0 = bottom. An f64 array takes rt_write_ppm_f64 — the reference's
@@ -629,6 +675,29 @@ class Renderer:
         _check(self.lib.rt_render_progressive(self.h, ctypes.byref(camera), ctypes.byref(params), batch_spp, cb,
                                               None, out.ctypes.data), "rt_render_progressive")
         return out
+
+    def render_adaptive(self, camera: Camera, params: RenderParams, min_spp: int, step_spp: int, threshold: float):
+        """rt_render_adaptive: the frame in passes, 8x8 tiles stopping once their noise estimate
+        E_t <= threshold (or at params.spp). Returns (mean height x width x 3, tile_spp and
+        tile_error per raster tile as (tiles_y, tiles_x) arrays, stderr_map height x width)."""
+        W, H = params.width, params.height
+        ty, tx = (H + 7) // 8, (W + 7) // 8
+        dt = np.float64 if params.out_format == RT_OUT_F64 else np.float32
+        mean = np.empty((H, W, 3), dtype=dt)
+        tile_spp = np.zeros((ty, tx), dtype=np.uint32)
+        tile_error = np.zeros((ty, tx), dtype=np.float64)
+        se = np.empty((H, W), dtype=np.float64)
+        params.out_on_device = 0
+        ap = AdaptiveParams(int(min_spp), int(step_spp), float(threshold))
+        out = AdaptiveOut(mean.ctypes.data, tile_spp.ctypes.data, tile_error.ctypes.data, se.ctypes.data)
+        _check(self.lib.rt_render_adaptive(self.h, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(ap),
+                                           ctypes.byref(out)), "rt_render_adaptive")
+        return mean, tile_spp, tile_error, se
+
+    def adaptive_stats(self) -> AdaptiveStats:
+        s = AdaptiveStats()
+        _check(self.lib.rt_adaptive_last_stats(self.h, ctypes.byref(s)), "rt_adaptive_last_stats")
+        return s
 
     def accumulator(self, params: RenderParams) -> "Accumulator":
         return Accumulator(self, params)

@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Tile-adaptive sampling (rt_render_adaptive) against the uniform rt_render on one config:
+overhead (threshold 0: the same samples in passes, through the moments kernel) and gain
+(samples traced, wall time and image error at a few thresholds).
+
+Each (library, mode list) runs in its own child process (RT_LIB_PATH picks the .so), the children
+one after another, `--rounds` times round-robin, and inside a child the modes alternate, so clock
+drift spreads over everything compared. A parent build (lib/librtiow_parent.so, built with
+__graft_entry__.build_library(csrc=<the parent commit's csrc>, name="librtiow_parent.so")) given
+with --parent runs the uniform mode only: it has no adaptive call.
+
+Times: wall ms of the synchronous call with a host f32 frame (host clock around a call that ends
+in a stream synchronise), and the HIP-event times the library reports. Bytes/s of the reductions:
+the per-sample records they read (24 B x samples traced) over their event time.
+Error: RMSE of sqrt(clamp(mean, 0, 0.999)) (the output's gamma) against a uniform render at
+--ref-mult x spp under another render seed, so the reference shares no sample with either frame.
+
+usage: python scripts/adaptive_bench.py --config C2 --thresholds 0.02 0.01 0.005 \
+           [--parent lib/librtiow_parent.so] [--min-spp 64 --step-spp 64] [--out adaptive_c2.json]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CONFIGS = {   # bench.py's
+    "C2": dict(scene=0, width=1200, height=800, spp=500, depth=50),
+    "C3": dict(scene=5, width=800, height=800, spp=1000, depth=50),
+    "C4": dict(scene=7, width=1920, height=1080, spp=1000, depth=50),
+}
+
+CHILD = r"""
+import json, os, sys, time
+sys.path.insert(0, {repo!r})
+import numpy as np
+import __graft_entry__ as ge
+rt = ge.import_binding()
+a = json.loads({args!r})
+W, H, spp = a["width"], a["height"], a["spp"]
+world = rt.World(1).build_scene(a["scene"])
+cam, bg = rt.scene_camera(a["scene"], W, H)
+r = rt.Renderer(0)
+r.upload(world)
+gamma = lambda x: np.sqrt(np.clip(x.astype(np.float64), 0.0, 0.999))
+ref = None
+if a["ref"]:
+    if not os.path.exists(a["ref"]):
+        p = rt.Renderer.params(W, H, spp * a["ref_mult"], a["depth"], bg, 2, out_format=rt.RT_OUT_F32)
+        np.save(a["ref"], r.render(cam, p))
+    ref = gamma(np.load(a["ref"]))
+res = {{}}
+def run(mode):
+    p = rt.Renderer.params(W, H, spp, a["depth"], bg, 1, out_format=rt.RT_OUT_F32)
+    t0 = time.perf_counter()
+    if mode == "uniform":
+        img = r.render(cam, p)
+        ms = (time.perf_counter() - t0) * 1e3
+        st = r.stats()
+        return img, dict(wall_ms=ms, trace_ms=st.kernel_ms, reduce_ms=st.reduce_ms, samples=st.samples,
+                         schedule=st.schedule, n_batches=st.n_batches)
+    img, tile_spp, tile_err, se = r.render_adaptive(cam, p, a["min_spp"], a["step_spp"], float(mode))
+    ms = (time.perf_counter() - t0) * 1e3
+    st = r.adaptive_stats()
+    d = st.as_dict()
+    d.update(wall_ms=ms, reduce_ms=st.moments_ms, samples=st.samples_traced, mean_tile_spp=float(tile_spp.mean()),
+             tiles_at_max=int((tile_spp == spp).sum()), tiles_at_min=int((tile_spp == st.min_spp).sum()),
+             tile_error_pct=[float(x) for x in np.percentile(tile_err, [5, 25, 50, 75, 95, 100])])
+    return img, d
+for mode in a["modes"]:
+    run(mode)                                  # warm-up: code objects, buffers
+for _ in range(a["reps"]):
+    for mode in a["modes"]:
+        img, d = run(mode)
+        e = res.setdefault(mode, dict(runs=[]))
+        e["runs"].append(d)
+        if ref is not None and "rmse" not in e:
+            e["rmse"] = float(np.sqrt(np.mean((gamma(img) - ref) ** 2)))
+print("RESULT", json.dumps(res))
+"""
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="C2", choices=sorted(CONFIGS))
+    ap.add_argument("--thresholds", type=float, nargs="*", default=[0.0])
+    ap.add_argument("--min-spp", type=int, default=64)
+    ap.add_argument("--step-spp", type=int, default=64)
+    ap.add_argument("--parent", default=None, help="a library built from the parent commit (uniform mode only)")
+    ap.add_argument("--lib", default=os.path.join("rust-ray-tracing-in-a-weekend_amd", "lib", "librtiow_amd.so"))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--ref-mult", type=int, default=4, help="the error reference: uniform at this many x spp (0: none)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    cfg = CONFIGS[a.config]
+    tmp = tempfile.TemporaryDirectory()   # the error reference: rendered by the first child, read by the others
+    ref = os.path.join(tmp.name, f"adaptive_ref_{a.config}_x{a.ref_mult}.npy") if a.ref_mult > 0 else None
+    jobs = [("new", a.lib, ["uniform"] + [repr(t) for t in a.thresholds])]
+    if a.parent:
+        jobs.insert(0, ("parent", a.parent, ["uniform"]))
+    runs = {}
+    for _ in range(a.rounds):
+        for name, lib, modes in jobs:
+            args = dict(cfg, modes=modes, reps=a.reps, min_spp=a.min_spp, step_spp=a.step_spp, ref=ref,
+                        ref_mult=a.ref_mult)
+            env = dict(os.environ, RT_LIB_PATH=os.path.abspath(os.path.join(REPO, lib)))
+            out = subprocess.run([sys.executable, "-c", CHILD.format(repo=REPO, args=json.dumps(args))], env=env,
+                                 capture_output=True, text=True, timeout=900)
+            if out.returncode != 0:
+                print(f"{name}: child failed ({out.returncode})\n{out.stderr[-2000:]}")
+                sys.exit(out.returncode if out.returncode > 0 else 1)
+            d = json.loads([x for x in out.stdout.splitlines() if x.startswith("RESULT ")][-1][7:])
+            for mode, e in d.items():
+                k = runs.setdefault(f"{name}:{mode}", dict(runs=[], rmse=e.get("rmse")))
+                k["runs"] += e["runs"]
+                print(f"  {name}:{mode}: wall {['%.2f' % x['wall_ms'] for x in e['runs']]}", flush=True)
+    uniform_px = cfg["width"] * cfg["height"] * cfg["spp"]
+    base = median([x["wall_ms"] for x in runs[("parent" if a.parent else "new") + ":uniform"]["runs"]])
+    summary = {}
+    for key, e in runs.items():
+        rs = e["runs"]
+        wall = [x["wall_ms"] for x in rs]
+        red = median([x["reduce_ms"] for x in rs])
+        s = dict(wall_ms_median=median(wall), wall_ms_min=min(wall), wall_ms_max=max(wall), n=len(wall),
+                 wall_over_base=median(wall) / base, trace_ms=median([x["trace_ms"] for x in rs]), reduce_ms=red,
+                 samples=rs[0]["samples"], samples_over_uniform=rs[0]["samples"] / uniform_px,
+                 reduce_GBps=rs[0]["samples"] * 24 / red / 1e6 if red > 0 else None, rmse=e["rmse"])
+        if "tile_error_pct" in rs[0]:
+            s["tile_error_pct_5_25_50_75_95_100"] = rs[0]["tile_error_pct"]
+        for k in ("passes", "classify_ms", "mean_tile_spp", "tiles_at_max", "tiles_at_min", "tiles", "schedule", "n_batches",
+                  "max_pass_batches"):
+            if k in rs[0]:
+                s[k] = median([x[k] for x in rs])
+        summary[key] = s
+        print(f"{a.config} {key}: " + json.dumps(s))
+    if a.out:
+        json.dump(dict(config=a.config, params=cfg, min_spp=a.min_spp, step_spp=a.step_spp, base_wall_ms=base,
+                       results=summary), open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
