@@ -5,20 +5,18 @@
 #include <algorithm>
 #include <array>
 #include <limits>
-#include <functional>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
-#include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include "rt/rt_abi.h"
 #include "adaptive_criterion.hpp"
 #include "ctx_internal.hpp"
+#include "scene_lower.hpp"
 #include "scene_model.hpp"
 #include "trace_kernel.hpp"
 
@@ -61,7 +59,7 @@ constexpr int kMaxLdsNodes = 512;
 #endif
 // instance BLAS nodes staged in LDS at most (64 B each)
 #ifndef RT_LDS_BLAS_MAX
-#define RT_LDS_BLAS_MAX 1024   // the LDS budget decides (512-thread final variant: 512 of the final scene's 548
+#define RT_LDS_BLAS_MAX 1024   // the LDS budget decides (512-thread final variant: 512 of the final scene's then 548
                                // BLAS nodes, 110.95 -> 108.23 ms at C4 1920x1080x100, r03r_ab_c4.log; with 256-thread
                                // workgroups the budget held ~95: 64 staged 132.15 ms, 16 133.31, none 132.98, r03h)
 #endif
@@ -524,395 +522,46 @@ int rt_world_flatten(rt_world* w, int accel, const rt_scene_soa** soa_out)
     return RT_OK;
 }
 
-// Stack entries a walk from `ref` needs, the way the kernel's visit uses its stack (push
-// the farther child when both are hit; with two identical child boxes child 0 is always
-// taken first, so only it stacks above the pushed child 1) — the rule flatten.cpp's
-// stack_need builds with, recomputed here from the tables alone. Iterative post-order
-// with three colours, so a cycle in a foreign node graph is found instead of walked
-// forever (the persistent kernel would spin on it). Returns -1 on a cycle.
-static int walk_need(const rt_scene_soa* s, int ref, std::vector<int>& need, std::vector<uint8_t>& colour)
-{
-    if (ref < 0) return 0;
-    std::vector<int> todo{ref};
-    while (!todo.empty()) {
-        const int i = todo.back();
-        if (colour[i] == 2) {
-            todo.pop_back();
-            continue;
-        }
-        const rt_bvh_node& nd = s->nodes[i];
-        if (colour[i] == 0) {
-            colour[i] = 1;  // on the current path
-            for (int ch : nd.child) {
-                if (ch < 0 || colour[ch] == 2) continue;
-                if (colour[ch] == 1) return -1;  // back edge
-                todo.push_back(ch);
-            }
-            continue;
-        }
-        todo.pop_back();  // both children done
-        auto nc = [&](int ch) { return ch < 0 ? 0 : need[ch]; };
-        const bool same = std::memcmp(nd.lo0, nd.lo1, 12) == 0 && std::memcmp(nd.hi0, nd.hi1, 12) == 0;
-        need[i] = same ? std::max(1 + nc(nd.child[0]), nc(nd.child[1])) : 1 + std::max(nc(nd.child[0]), nc(nd.child[1]));
-        colour[i] = 2;
-    }
-    return need[ref];
-}
-
-// SceneDev.pre_leaf: a root child that is a leaf of <= 2 primitives whose box holds at least
-// 8x the volume of its sibling's (a ground or fog sphere around the whole scene) is tested
-// before the walk, which then starts at the sibling (in the kernel variants that do this). The closest hit does not depend on the
-// order of the tests, so the image does not change (tests/test_gpu_parity.py); only SAH
-// tables (the LINEAR / MEDIAN modes keep the reference's structures as they are).
-static void hoist_root_leaf(const rt_scene_soa* s, rtk::SceneDev& S)
-{
-    if (s->accel != RT_ACCEL_SAH || s->tlas_root < 0 || s->tlas_root >= s->n_nodes) return;
-    const rt_bvh_node& root = s->nodes[s->tlas_root];
-    auto volume = [](const float* lo, const float* hi) {
-        double v = 1.0;
-        for (int a = 0; a < 3; ++a) v *= std::max(0.0, (double)hi[a] - (double)lo[a]);
-        return v;
-    };
-    for (int c = 0; c < 2; ++c) {
-        const int leaf = root.child[c], other = root.child[1 - c];
-        if (leaf >= 0 || (~leaf & 31) > 2) continue;
-        const float* lo = c ? root.lo1 : root.lo0;
-        const float* hi = c ? root.hi1 : root.hi0;
-        const double v = volume(lo, hi), vo = volume(c ? root.lo0 : root.lo1, c ? root.hi0 : root.hi1);
-        if (!(v >= 8.0 * vo) || !std::isfinite(v)) continue;
-        S.pre_leaf = leaf;
-        for (int a = 0; a < 3; ++a) {
-            S.pre_lo[a] = lo[a];
-            S.pre_hi[a] = hi[a];
-        }
-        S.pre_root = other;
-        return;
-    }
-}
-
-// Validates a (possibly foreign) SoA so the kernel never indexes out of bounds, never
-// overruns its traversal stack and never walks a cycle; computes the stack needs itself
-// (the tlas_depth / blas_depth fields are not trusted) and whether the TLAS really lies in
-// nodes[0, n_tlas_nodes) (the kernel copies that prefix into LDS and then reads only LDS).
-static int validate_soa(const rt_scene_soa* s, int& tlas_depth, int& blas_depth, int& n_tlas_nodes)
-{
-    if (s->n_prim_refs >= (1 << 26) - 64) return fail(RT_ERR_UNSUPPORTED, "too many primitive references");
-    if (s->n_prims < 0 || s->n_prim_refs < 0 || s->n_nodes < 0 || s->n_instances < 0 || s->n_materials < 0 ||
-        s->n_textures < 0 || s->n_perlin < 0 || s->image_bytes < 0)
-        return fail(RT_ERR_INVALID, "negative table size");
-    if ((s->n_prims && !s->prims) || (s->n_prim_refs && !s->prim_refs) || (s->n_nodes && !s->nodes) ||
-        (s->n_instances && !s->instances) || (s->n_materials && !s->materials) || (s->n_textures && !s->textures) ||
-        (s->n_perlin && (!s->perlin_ranvec || !s->perlin_perm)) || (s->image_bytes && !s->image_data))
-        return fail(RT_ERR_INVALID, "null table");
-    auto simple_kind = [](int k) { return k >= RT_PRIM_SPHERE && k <= RT_PRIM_BOX; };
-    for (int i = 0; i < s->n_prims; ++i) {
-        const rt_prim& p = s->prims[i];
-        if (p.kind < RT_PRIM_SPHERE || p.kind > RT_PRIM_MEDIUM) return fail(RT_ERR_INVALID, "bad prim kind");
-        if (p.kind == RT_PRIM_INSTANCE && (p.a < 0 || p.a >= s->n_instances)) return fail(RT_ERR_INVALID, "bad instance");
-        if (p.kind == RT_PRIM_MEDIUM) {
-            if (p.a < 0 || p.a >= s->n_prims) return fail(RT_ERR_INVALID, "bad boundary");
-            const int bk = s->prims[p.a].kind;  // boundary_t: a simple prim or an instance
-            if (!simple_kind(bk) && bk != RT_PRIM_INSTANCE) return fail(RT_ERR_UNSUPPORTED, "medium boundary kind");
-        }
-        if (p.kind != RT_PRIM_INSTANCE && (p.mat < 0 || p.mat >= s->n_materials)) return fail(RT_ERR_INVALID, "bad material");
-    }
-    for (int i = 0; i < s->n_materials; ++i) {
-        const rt_material& m = s->materials[i];
-        if (m.kind < RT_MAT_LAMBERTIAN || m.kind > RT_MAT_ISOTROPIC) return fail(RT_ERR_INVALID, "bad material kind");
-        bool needs_tex = m.kind == RT_MAT_LAMBERTIAN || m.kind == RT_MAT_DIFFUSE_LIGHT || m.kind == RT_MAT_ISOTROPIC;
-        if (needs_tex && (m.tex < 0 || m.tex >= s->n_textures)) return fail(RT_ERR_INVALID, "bad texture ref");
-    }
-    for (int i = 0; i < s->n_textures; ++i) {
-        const rt_texture& t = s->textures[i];
-        if (t.kind < RT_TEX_SOLID || t.kind > RT_TEX_IMAGE) return fail(RT_ERR_INVALID, "bad texture kind");
-        if (t.kind == RT_TEX_NOISE && (t.perlin < 0 || t.perlin >= s->n_perlin)) return fail(RT_ERR_INVALID, "bad perlin");
-        if (t.kind == RT_TEX_IMAGE && t.img_w > 0 &&
-            (t.img_h <= 0 || t.img_offset < 0 || t.img_bps < 3 * (int64_t)t.img_w ||
-             t.img_offset + t.img_bps * (int64_t)(t.img_h - 1) + 3 * (int64_t)t.img_w > s->image_bytes))
-            return fail(RT_ERR_INVALID, "image texture out of range");
-    }
-    for (int i = 0; i < s->n_prim_refs; ++i)
-        if (s->prim_refs[i] < 0 || s->prim_refs[i] >= s->n_prims) return fail(RT_ERR_INVALID, "bad prim ref");
-    auto check_ref = [&](int ref) {
-        if (ref >= 0) return ref < s->n_nodes;
-        int code = ~ref;
-        return (code >> 5) + (code & 31) <= s->n_prim_refs;
-    };
-    for (int i = 0; i < s->n_nodes; ++i)
-        if (!check_ref(s->nodes[i].child[0]) || !check_ref(s->nodes[i].child[1])) return fail(RT_ERR_INVALID, "bad node");
-    if (!check_ref(s->tlas_root)) return fail(RT_ERR_INVALID, "bad tlas root");
-    for (int i = 0; i < s->n_instances; ++i) {
-        const rt_instance& in = s->instances[i];
-        if (in.n_ops < 0 || in.n_ops > 4) return fail(RT_ERR_INVALID, "bad instance ops");
-        if (in.child_kind != RT_CHILD_PRIM && in.child_kind != RT_CHILD_BVH) return fail(RT_ERR_INVALID, "bad instance child kind");
-        if (in.child_kind == RT_CHILD_PRIM ? (in.child < 0 || in.child >= s->n_prims) : !check_ref(in.child))
-            return fail(RT_ERR_INVALID, "bad instance child");
-        if (in.child_kind == RT_CHILD_PRIM && !simple_kind(s->prims[in.child].kind) &&
-            s->prims[in.child].kind != RT_PRIM_MEDIUM)
-            return fail(RT_ERR_UNSUPPORTED, "instance child must be a primitive, a medium or a BVH");
-    }
-    // what the kernel's nested calls assume (flatten.cpp lowers any nesting into this shape):
-    // a medium's boundary instance has no medium child (no recursion), and an instance BLAS
-    // holds simple primitives only
-    for (int i = 0; i < s->n_prims; ++i) {
-        const rt_prim& p = s->prims[i];
-        if (p.kind != RT_PRIM_MEDIUM || s->prims[p.a].kind != RT_PRIM_INSTANCE) continue;
-        const rt_instance& in = s->instances[s->prims[p.a].a];
-        if (in.child_kind == RT_CHILD_PRIM && s->prims[in.child].kind == RT_PRIM_MEDIUM)
-            return fail(RT_ERR_UNSUPPORTED, "a medium's boundary holds a medium");
-    }
-    // stack needs (the kernel: TLAS walk in entries [0, tlas), a nested BLAS walk above it)
-    std::vector<int> need((size_t)s->n_nodes, 0);
-    std::vector<uint8_t> colour((size_t)s->n_nodes, 0);
-    const int t = walk_need(s, s->tlas_root, need, colour);
-    if (t < 0) return fail(RT_ERR_INVALID, "cycle in the TLAS node graph");
-    tlas_depth = t + 1;  // + 1 as flatten.cpp records it
-    blas_depth = 0;
-    // Each node's need depends only on its subtree, and a completed walk leaves every node it
-    // reached done (colour 2) with its need recorded, so the walks of instance BLASes share
-    // one colour array: a BLAS shared by many instances, or a subtree of one already walked,
-    // costs nothing the second time (O(nodes) in total, not O(instances x nodes)). Likewise
-    // `checked` marks subtrees whose leaves were already found to hold simple primitives.
-    std::vector<uint8_t> checked((size_t)s->n_nodes, 0);
-    for (int i = 0; i < s->n_instances; ++i) {
-        const rt_instance& in = s->instances[i];
-        if (in.child_kind != RT_CHILD_BVH) continue;
-        const int b = walk_need(s, in.child, need, colour);
-        if (b < 0) return fail(RT_ERR_INVALID, "cycle in an instance BVH");
-        blas_depth = std::max(blas_depth, b + 1);
-        std::vector<int> todo{in.child};   // acyclic (checked above): every leaf slot is a simple prim
-        while (!todo.empty()) {
-            const int ref = todo.back();
-            todo.pop_back();
-            if (ref >= 0) {
-                if (checked[ref]) continue;
-                checked[ref] = 1;
-                todo.push_back(s->nodes[ref].child[0]);
-                todo.push_back(s->nodes[ref].child[1]);
-                continue;
-            }
-            const int code = ~ref;
-            for (int j = code >> 5; j < (code >> 5) + (code & 31); ++j)
-                if (!simple_kind(s->prims[s->prim_refs[j]].kind))
-                    return fail(RT_ERR_UNSUPPORTED, "an instance BVH holds a non-primitive");
-        }
-    }
-    if (tlas_depth > 32 || blas_depth > 32) return fail(RT_ERR_UNSUPPORTED, "BVH too deep for the traversal stack");
-    // the TLAS-in-LDS claim: every node reachable from the root lies in [0, n_tlas_nodes)
-    n_tlas_nodes = 0;
-    if (s->n_tlas_nodes > 0 && s->n_tlas_nodes <= s->n_nodes && s->tlas_root == 0) {
-        bool inside = true;
-        std::vector<int> todo{0};
-        std::fill(colour.begin(), colour.end(), 0);
-        while (!todo.empty() && inside) {
-            const int i = todo.back();
-            todo.pop_back();
-            if (i >= s->n_tlas_nodes) inside = false;
-            if (!inside || colour[i]) continue;
-            colour[i] = 1;
-            for (int ch : s->nodes[i].child)
-                if (ch >= 0) todo.push_back(ch);
-        }
-        if (inside) n_tlas_nodes = s->n_tlas_nodes;
-    }
-    return RT_OK;
-}
-
 int rt_scene_validate(const rt_scene_soa* s, int32_t* tlas_depth, int32_t* blas_depth)
 {
     if (!s) return fail(RT_ERR_INVALID, "null argument");
     int t = 0, b = 0, n = 0;
-    int rc = validate_soa(s, t, b, n);
-    if (rc) return rc;
+    std::string err;
+    const int rc = rtl::validate(*s, t, b, n, err);
+    if (rc) return fail(rc, err);
     if (tlas_depth) *tlas_depth = t;
     if (blas_depth) *blas_depth = b;
     return RT_OK;
 }
 
+// Everything the kernels assume about the scene is decided on the host by rtl::lower
+// (scene_lower.cpp); this copies its tables and the SoA's others into one device allocation
+// (256-B aligned tables) and records the rest in the context.
 int rt_ctx_upload_soa(rt_ctx* c, const rt_scene_soa* s)
 {
     if (!c || !s) return fail(RT_ERR_INVALID, "null argument");
-    int tlas_depth = 0, blas_depth = 0, n_tlas_nodes = 0;
-    int vrc = validate_soa(s, tlas_depth, blas_depth, n_tlas_nodes);
-    if (vrc) return vrc;
+    rtl::Lowered L;
+    std::string err;
+    const int rc = rtl::lower(*s, c->opt_hoist != 0, L, err);
+    if (rc) return fail(rc, err);
 
-    // The device's primitive records. A Sphere is stored as a MovingSphere that does not
-    // move (velocity 0, a = 1: the centre c0 + 0 * time is c0 bit for bit), so the kernel's
-    // sphere test reads no kind and selects nothing (sphere_center). Then the records in
-    // leaf-slot order (prims[prim_refs[j]]): the leaf loops read a record without first
-    // loading its index.
-    // A MovingSphere's a says whether its shutter is [0, 1] ((time - 0) / (1 - 0) is time
-    // exactly); it is recomputed here rather than trusted from a foreign SoA. Only a scene
-    // with another shutter needs FEAT_SHUTTER (the per-primitive flag and the division);
-    // without it a sphere test issues all its loads at once.
-    std::vector<rt_prim> prims(s->prims, s->prims + s->n_prims);
-    bool general_shutter = false;
-    for (rt_prim& p : prims) {
-        if (p.kind == RT_PRIM_SPHERE) {
-            p.a = 1;
-            p.p[5] = p.p[6] = p.p[7] = 0.0;
-            p.p[8] = 0.0;
-            p.p[9] = 1.0;
-        } else if (p.kind == RT_PRIM_MOVING_SPHERE) {
-            p.a = (p.p[8] == 0.0 && p.p[9] == 1.0) ? 1 : 0;
-            if (!p.a) general_shutter = true;
-        } else if (p.kind == RT_PRIM_INSTANCE) {
-            // b = 1: the instance's child is a BVH (the kernel defers the first such walk of a
-            // cast, RT_DEFER_INST); a single child primitive is tested where the walk meets it
-            p.b = s->instances[p.a].child_kind == RT_CHILD_BVH ? 1 : 0;
-        }
-    }
-    std::vector<rt_prim> leaf_prims((size_t)s->n_prim_refs);
-    for (int j = 0; j < s->n_prim_refs; ++j) leaf_prims[(size_t)j] = prims[(size_t)s->prim_refs[j]];
-    // Device copies of the nodes and instances in which every instance BLAS's leaf codes count
-    // slots from that BLAS's first leaf slot (kept in the device rt_instance.pad): the codes of
-    // both walks then stay small enough for 16-bit stack entries (Stack16: the final scene's
-    // 1000-sphere BLAS has slots 410..1409, relative 0..999). Only when every BLAS is disjoint
-    // from the TLAS and from the other BLASes (or shares a BLAS with its base); otherwise the
-    // codes stay absolute and the scene takes the 32-bit stack (stack16_ok 0).
-    std::vector<rt_bvh_node> nodes_dev(s->nodes, s->nodes + s->n_nodes);
-    std::vector<rt_instance> inst_dev(s->instances, s->instances + s->n_instances);
-    for (rt_instance& in : inst_dev) in.pad = 0;
-    int max_code = 0;             // the largest leaf code ((first slot << 5) | count) either walk pushes
-    bool rel_ok = true;
-    {
-        auto leaf_first = [](int ref) { return (~ref) >> 5; };
-        std::vector<int> owner((size_t)s->n_nodes, -1);   // -2: TLAS; else the BLAS base
-        std::vector<int> todo;
-        if (s->tlas_root >= 0) todo.push_back(s->tlas_root);
-        else max_code = std::max(max_code, ~s->tlas_root);
-        while (!todo.empty()) {   // validate_soa checked refs and acyclicity
-            const int i = todo.back();
-            todo.pop_back();
-            if (owner[(size_t)i] == -2) continue;
-            owner[(size_t)i] = -2;
-            for (int ch : s->nodes[i].child) {
-                if (ch >= 0) todo.push_back(ch);
-                else max_code = std::max(max_code, ~ch);
-            }
-        }
-        // each BLAS root is walked once however many instances share it (memo: root -> base),
-        // over one epoch-stamped visited array
-        std::unordered_map<int, int> root_base;
-        std::vector<uint32_t> seen((size_t)s->n_nodes, 0);
-        uint32_t epoch = 0;
-        for (size_t ii = 0; ii < inst_dev.size() && rel_ok; ++ii) {
-            rt_instance& in = inst_dev[ii];
-            if (in.child_kind != RT_CHILD_BVH) continue;
-            if (in.child >= 0) {
-                const auto m = root_base.find(in.child);
-                if (m != root_base.end()) {
-                    in.pad = m->second;
-                    continue;
-                }
-            }
-            std::vector<int> blas;   // the BLAS's nodes, and its smallest leaf slot
-            int base = 1 << 30;
-            const int root = in.child;
-            if (in.child < 0) base = leaf_first(in.child);
-            else todo.push_back(in.child);
-            ++epoch;
-            while (!todo.empty()) {
-                const int i = todo.back();
-                todo.pop_back();
-                if (seen[(size_t)i] == epoch) continue;
-                seen[(size_t)i] = epoch;
-                blas.push_back(i);
-                for (int ch : s->nodes[i].child) {
-                    if (ch >= 0) todo.push_back(ch);
-                    else base = std::min(base, leaf_first(ch));
-                }
-            }
-            for (int i : blas)
-                if (owner[(size_t)i] == -2 || (owner[(size_t)i] >= 0 && owner[(size_t)i] != base)) rel_ok = false;
-            if (!rel_ok) break;
-            auto rel = [&](int ref) {
-                const int code = ~ref;
-                const int first = (code >> 5) - base;
-                const int rcode = (first << 5) | (code & 31);
-                max_code = std::max(max_code, rcode);
-                return ~rcode;
-            };
-            for (int i : blas) {
-                if (owner[(size_t)i] == base) continue;   // shared with an instance already rewritten
-                owner[(size_t)i] = base;
-                for (int& ch : nodes_dev[(size_t)i].child)
-                    if (ch < 0) ch = rel(ch);
-            }
-            if (in.child < 0) in.child = rel(in.child);
-            else root_base.emplace(root, base);
-            in.pad = base;
-        }
-        if (!rel_ok) {   // absolute codes everywhere
-            nodes_dev.assign(s->nodes, s->nodes + s->n_nodes);
-            inst_dev.assign(s->instances, s->instances + s->n_instances);
-            for (rt_instance& in : inst_dev) in.pad = 0;
-            max_code = (s->n_prim_refs << 5) | 31;
-        }
-    }
-    // The largest instance BLAS in BFS order right after the TLAS prefix (device node order
-    // only): a launch stages its top levels in LDS (SceneDev.n_lds_blas), where the nested
-    // walk reads them instead of waiting on L2 for every level. Needs the TLAS prefix and a
-    // BLAS disjoint from it (validate_soa's n_tlas_nodes); otherwise nothing is staged.
-    int n_blas_bfs = 0;
-    {
-        int best_root = -1;
-        size_t best_n = 0;
-        std::vector<int> bfs;
-        std::unordered_set<int> walked;   // each BLAS root once, over one epoch-stamped array
-        std::vector<uint32_t> seen((size_t)s->n_nodes, 0);
-        uint32_t epoch = 0;
-        for (const rt_instance& in : inst_dev) {
-            if (in.child_kind != RT_CHILD_BVH || in.child < n_tlas_nodes) continue;
-            if (!walked.insert(in.child).second) continue;
-            std::vector<int> order{in.child};
-            ++epoch;
-            seen[(size_t)in.child] = epoch;
-            bool disjoint = true;
-            for (size_t i = 0; i < order.size(); ++i)
-                for (int ch : nodes_dev[(size_t)order[i]].child)
-                    if (ch >= 0 && seen[(size_t)ch] != epoch) {
-                        seen[(size_t)ch] = epoch;
-                        if (ch < n_tlas_nodes) disjoint = false;
-                        order.push_back(ch);
-                    }
-            if (disjoint && order.size() > best_n) {
-                best_n = order.size();
-                best_root = in.child;
-                bfs.swap(order);
-            }
-        }
-        if (best_root >= 0 && (n_tlas_nodes > 0 || s->tlas_root < 0)) {
-            std::vector<int> perm((size_t)s->n_nodes, -1);
-            for (int i = 0; i < n_tlas_nodes; ++i) perm[(size_t)i] = i;
-            int next = n_tlas_nodes;
-            for (int b : bfs) perm[(size_t)b] = next++;
-            for (int i = 0; i < s->n_nodes; ++i)
-                if (perm[(size_t)i] < 0) perm[(size_t)i] = next++;
-            std::vector<rt_bvh_node> moved((size_t)s->n_nodes);
-            for (int i = 0; i < s->n_nodes; ++i) {
-                rt_bvh_node nd = nodes_dev[(size_t)i];
-                for (int& ch : nd.child)
-                    if (ch >= 0) ch = perm[(size_t)ch];
-                moved[(size_t)perm[(size_t)i]] = nd;
-            }
-            nodes_dev.swap(moved);
-            for (rt_instance& in : inst_dev)
-                if (in.child_kind == RT_CHILD_BVH && in.child >= 0) in.child = perm[(size_t)in.child];
-            n_blas_bfs = (int)bfs.size();
-        }
-    }
-    size_t off[10], bytes[10] = {
-        (size_t)s->n_nodes * sizeof(rt_bvh_node), (size_t)s->n_prim_refs * 4, (size_t)s->n_prims * sizeof(rt_prim),
-        (size_t)s->n_instances * sizeof(rt_instance), (size_t)s->n_materials * sizeof(rt_material),
-        (size_t)s->n_textures * sizeof(rt_texture), (size_t)s->n_perlin * 768 * 8, (size_t)s->n_perlin * 768 * 4,
-        (size_t)s->image_bytes, (size_t)s->n_prim_refs * sizeof(rt_prim)};
-    const void* src[10] = {nodes_dev.data(), s->prim_refs, prims.data(), inst_dev.data(), s->materials, s->textures,
-                           s->perlin_ranvec, s->perlin_perm, s->image_data, leaf_prims.data()};
+    struct Table {
+        const void* src;
+        size_t bytes, off;
+    } t[10] = {{L.nodes.data(), L.nodes.size() * sizeof(rt_bvh_node), 0},
+               {s->prim_refs, (size_t)s->n_prim_refs * 4, 0},
+               {L.prims.data(), L.prims.size() * sizeof(rt_prim), 0},
+               {L.instances.data(), L.instances.size() * sizeof(rt_instance), 0},
+               {s->materials, (size_t)s->n_materials * sizeof(rt_material), 0},
+               {s->textures, (size_t)s->n_textures * sizeof(rt_texture), 0},
+               {s->perlin_ranvec, (size_t)s->n_perlin * 768 * 8, 0},
+               {s->perlin_perm, (size_t)s->n_perlin * 768 * 4, 0},
+               {s->image_data, (size_t)s->image_bytes, 0},
+               {L.leaf_prims.data(), L.leaf_prims.size() * sizeof(rt_prim), 0}};
     size_t total = 0;
-    for (int i = 0; i < 10; ++i) {
-        off[i] = total;
-        total = align_up(total + bytes[i], 256);
+    for (Table& e : t) {
+        e.off = total;
+        total = align_up(total + e.bytes, 256);
     }
     total = std::max<size_t>(total, 256);
     HIP_TRY(hipSetDevice(c->device));
@@ -926,211 +575,40 @@ int rt_ctx_upload_soa(rt_ctx* c, const rt_scene_soa* s)
         c->scene_bytes = total;
     }
     char* base = (char*)c->scene_buf;
-    for (int i = 0; i < 10; ++i)
-        if (bytes[i]) HIP_TRY(hipMemcpy(base + off[i], src[i], bytes[i], hipMemcpyHostToDevice));
-    c->S.nodes = (const rt_bvh_node*)(base + off[0]);
-    c->S.prim_refs = (const int32_t*)(base + off[1]);
-    c->S.prims = (const rt_prim*)(base + off[2]);
-    c->S.instances = (const rt_instance*)(base + off[3]);
-    c->S.materials = (const rt_material*)(base + off[4]);
-    c->S.textures = (const rt_texture*)(base + off[5]);
-    c->S.perlin_ranvec = (const double*)(base + off[6]);
-    c->S.perlin_perm = (const int32_t*)(base + off[7]);
-    c->S.image = (const uint8_t*)(base + off[8]);
-    c->S.leaf_prims = (const rt_prim*)(base + off[9]);
-    c->S.tlas_root = s->tlas_root;
-    c->S.pre_leaf = 0;
-    if (c->opt_hoist) hoist_root_leaf(s, c->S);
-    // Stack16 (trace_device.hpp): node records at LDS addresses < 32 KB (80 B each), BLAS node
-    // indices < 32768, and leaf codes ((first slot << 5) | count, stored complemented; BLAS slots
-    // relative, above) strictly above the -32768 = ~32767 sentinel: every code < 32767 (a leaf
-    // at first slot 1023 holding 31 primitives would complement to the sentinel itself)
-    c->S.stack16_ok = (n_tlas_nodes * (int64_t)80 <= 32767 - 80 && max_code < 32767 && s->n_nodes <= 32767) ? 1 : 0;
-    c->S.n_lds_nodes = 0;
-    c->S.n_blas_bfs = n_blas_bfs;
-    c->S.n_lds_blas = 0;
-    // traversal stack: TLAS walk, then a nested BLAS walk (instances) above it, sized from the
-    // depths validate_soa measured (<= 32 each), each walk's bottom entry holding its RT_DONE
-    // sentinel (traverse): the 66-entry scratch stack always fits
-    c->S.blas_base = tlas_depth + 1;
-    c->S.stack_entries = tlas_depth + 1 + (blas_depth > 0 ? blas_depth + 1 : 0);
-    // A BLAS walk nests in the top-level walk only for a cast's second instance over a BVH (the
-    // first is deferred until the top-level walk ends, then walks from entry 0: RT_DEFER_INST),
-    // an instance over a medium, or a medium whose boundary is an instance. A scene whose top
-    // level holds one instance over a BVH and none of the others (the final scene) needs the
-    // larger of the two walks, not their sum: 13 entries instead of 25 per lane, 12 KB less LDS
-    // per block.
-    if (RT_DEFER_INST && blas_depth > 0) {
-        int n_inst = 0;
-        bool inst_boundary = false;
-        std::vector<int> todo{s->tlas_root};
-        while (!todo.empty()) {
-            const int ref = todo.back();
-            todo.pop_back();
-            if (ref >= 0) {   // acyclic and in range (validate_soa)
-                todo.push_back(s->nodes[ref].child[0]);
-                todo.push_back(s->nodes[ref].child[1]);
-                continue;
-            }
-            const int code = ~ref;
-            for (int j = code >> 5; j < (code >> 5) + (code & 31); ++j) {
-                const rt_prim& p = s->prims[s->prim_refs[j]];
-                if (p.kind == RT_PRIM_INSTANCE) {   // an instance that may walk a BLAS
-                    const rt_instance& in = s->instances[p.a];
-                    if (in.child_kind == RT_CHILD_BVH) ++n_inst;
-                    else if (s->prims[in.child].kind == RT_PRIM_MEDIUM) inst_boundary = true;   // never deferred
-                }
-                if (p.kind == RT_PRIM_MEDIUM && s->prims[p.a].kind == RT_PRIM_INSTANCE) inst_boundary = true;
-            }
-        }
-        if (n_inst <= 1 && !inst_boundary) c->S.stack_entries = std::max(tlas_depth + 1, blas_depth + 1);
-    }
-    c->n_tlas_nodes = n_tlas_nodes;
+    for (const Table& e : t)
+        if (e.bytes) HIP_TRY(hipMemcpy(base + e.off, e.src, e.bytes, hipMemcpyHostToDevice));
+
+    rtk::SceneDev& S = c->S;
+    S.nodes = (const rt_bvh_node*)(base + t[0].off);
+    S.prim_refs = (const int32_t*)(base + t[1].off);
+    S.prims = (const rt_prim*)(base + t[2].off);
+    S.instances = (const rt_instance*)(base + t[3].off);
+    S.materials = (const rt_material*)(base + t[4].off);
+    S.textures = (const rt_texture*)(base + t[5].off);
+    S.perlin_ranvec = (const double*)(base + t[6].off);
+    S.perlin_perm = (const int32_t*)(base + t[7].off);
+    S.image = (const uint8_t*)(base + t[8].off);
+    S.leaf_prims = (const rt_prim*)(base + t[9].off);
+    S.tlas_root = s->tlas_root;
+    S.pre_leaf = L.pre_leaf;
+    S.pre_root = L.pre_root;
+    std::copy(L.pre_lo, L.pre_lo + 3, S.pre_lo);
+    std::copy(L.pre_hi, L.pre_hi + 3, S.pre_hi);
+    S.stack16_ok = L.stack16_ok;
+    S.blas_base = L.blas_base;
+    S.stack_entries = L.stack_entries;
+    S.n_tlas_nodes = L.n_tlas_nodes;
+    S.n_blas_bfs = L.n_blas_bfs;
+    S.n_lds_nodes = S.n_lds_blas = 0;   // a launch decides what it stages in LDS
+    S.has_lights = L.has_lights;
+    S.has_spheres = L.has_spheres;
+    c->n_tlas_nodes = L.n_tlas_nodes;
     c->n_nodes = s->n_nodes;
     c->n_materials = s->n_materials;
     c->n_textures = s->n_textures;
-    c->S.n_tlas_nodes = c->n_tlas_nodes;
+    c->features = L.features;
+    c->pad_extent = L.pad_extent;
     c->has_scene = true;
-    uint32_t feat = 0;
-    for (int i = 0; i < s->n_prims; ++i) {
-        const int k = s->prims[i].kind;
-        if (k == RT_PRIM_XY_RECT || k == RT_PRIM_XZ_RECT || k == RT_PRIM_YZ_RECT || k == RT_PRIM_BOX) feat |= rtk::FEAT_RECT;
-        if (k == RT_PRIM_INSTANCE) feat |= rtk::FEAT_INST;
-        if (k == RT_PRIM_MEDIUM) feat |= rtk::FEAT_MEDIUM;
-    }
-    // what instances and medium boundaries reach (the kernel variant drops the rest there):
-    // rects / boxes under an instance, and medium boundaries other than spheres
-    auto is_rect = [](int k) {
-        return k == RT_PRIM_XY_RECT || k == RT_PRIM_XZ_RECT || k == RT_PRIM_YZ_RECT || k == RT_PRIM_BOX;
-    };
-    for (int i = 0; i < s->n_instances; ++i) {
-        const rt_instance& in = s->instances[i];
-        if (in.child_kind == RT_CHILD_PRIM) {
-            const int ck = s->prims[in.child].kind;
-            if (is_rect(ck)) feat |= rtk::FEAT_INST_RECT;
-            if (ck == RT_PRIM_MEDIUM) {
-                feat |= rtk::FEAT_INST_MEDIUM | rtk::FEAT_MEDIUM;
-                const int bk = s->prims[s->prims[in.child].a].kind;   // its boundary, tested in object space
-                if (bk != RT_PRIM_SPHERE && bk != RT_PRIM_MOVING_SPHERE) feat |= rtk::FEAT_MEDIUM_INST;
-            }
-            continue;
-        }
-        feat |= rtk::FEAT_INST_BLAS;
-        std::vector<int> todo{in.child};   // validate_soa checked refs and acyclicity
-        while (!todo.empty() && !(feat & rtk::FEAT_INST_RECT)) {
-            const int ref = todo.back();
-            todo.pop_back();
-            if (ref >= 0) {
-                todo.push_back(s->nodes[ref].child[0]);
-                todo.push_back(s->nodes[ref].child[1]);
-                continue;
-            }
-            const int code = ~ref, first = code >> 5, count = code & 31;
-            for (int j = first; j < first + count; ++j)
-                if (is_rect(s->prims[s->prim_refs[j]].kind)) feat |= rtk::FEAT_INST_RECT;
-        }
-    }
-    for (int i = 0; i < s->n_prims; ++i)
-        if (s->prims[i].kind == RT_PRIM_MEDIUM) {
-            const int bk = s->prims[s->prims[i].a].kind;
-            if (bk != RT_PRIM_SPHERE && bk != RT_PRIM_MOVING_SPHERE) feat |= rtk::FEAT_MEDIUM_INST;
-        }
-    for (int i = 0; i < s->n_textures; ++i) {
-        if (s->textures[i].kind == RT_TEX_NOISE) feat |= rtk::FEAT_NOISE;
-        if (s->textures[i].kind == RT_TEX_IMAGE) feat |= rtk::FEAT_IMAGE;
-    }
-    // FEAT_IMAGE_UV: an image-textured primitive whose hit record must carry its uv inputs (a rect
-    // or box, or anything under an instance); otherwise uv comes from a top-level sphere's normal
-    if (feat & rtk::FEAT_IMAGE) {
-        auto imaged = [&](const rt_prim& p) {
-            if (p.kind == RT_PRIM_INSTANCE || p.kind == RT_PRIM_MEDIUM) return false;
-            const int m = p.mat;
-            return m >= 0 && m < s->n_materials && s->materials[m].kind != RT_MAT_METAL &&
-                   s->materials[m].kind != RT_MAT_DIELECTRIC && s->materials[m].tex >= 0 &&
-                   s->materials[m].tex < s->n_textures && s->textures[s->materials[m].tex].kind == RT_TEX_IMAGE;
-        };
-        std::vector<uint8_t> under((size_t)s->n_prims, 0);   // reached through an instance
-        for (int i = 0; i < s->n_instances; ++i) {
-            const rt_instance& in = s->instances[i];
-            if (in.child_kind == RT_CHILD_PRIM) {
-                under[(size_t)in.child] = 1;
-                continue;
-            }
-            std::vector<int> todo{in.child};
-            while (!todo.empty()) {
-                const int ref = todo.back();
-                todo.pop_back();
-                if (ref >= 0) {
-                    todo.push_back(s->nodes[ref].child[0]);
-                    todo.push_back(s->nodes[ref].child[1]);
-                    continue;
-                }
-                const int code = ~ref;
-                for (int j = code >> 5; j < (code >> 5) + (code & 31); ++j) under[(size_t)s->prim_refs[j]] = 1;
-            }
-        }
-        for (int i = 0; i < s->n_prims; ++i) {
-            const rt_prim& p = s->prims[i];
-            if (imaged(p) && (under[(size_t)i] || (p.kind != RT_PRIM_SPHERE && p.kind != RT_PRIM_MOVING_SPHERE)))
-                feat |= rtk::FEAT_IMAGE_UV;
-        }
-    }
-    if (general_shutter) feat |= rtk::FEAT_SHUTTER;
-    // FEAT_NEST_MOVING: a sphere that really moves (nonzero velocity, or a shutter other than
-    // [0, 1], whose centre may not be c0) under an instance or inside a medium boundary; without
-    // it the kernel tests spheres there as static (FEAT_STATIC: c0, no velocity loads)
-    {
-        auto moving = [&](int i) {
-            const rt_prim& q = prims[(size_t)i];
-            return q.kind == RT_PRIM_MOVING_SPHERE && (!q.a || q.p[5] != 0.0 || q.p[6] != 0.0 || q.p[7] != 0.0);
-        };
-        std::vector<uint8_t> seen((size_t)s->n_nodes, 0);
-        auto bvh_moving = [&](int root) {   // validate_soa checked refs and acyclicity
-            std::vector<int> todo{root};
-            while (!todo.empty()) {
-                const int ref = todo.back();
-                todo.pop_back();
-                if (ref >= 0) {
-                    if (seen[(size_t)ref]) continue;
-                    seen[(size_t)ref] = 1;
-                    todo.push_back(s->nodes[ref].child[0]);
-                    todo.push_back(s->nodes[ref].child[1]);
-                    continue;
-                }
-                const int code = ~ref;
-                for (int j = code >> 5; j < (code >> 5) + (code & 31); ++j)
-                    if (moving(s->prim_refs[j])) return true;
-            }
-            return false;
-        };
-        // an instance's child prim (a medium: its boundary, which holds no medium) or BLAS
-        std::function<bool(int)> inst_moving = [&](int ii) {
-            const rt_instance& in = s->instances[ii];
-            if (in.child_kind == RT_CHILD_BVH) return bvh_moving(in.child);
-            const rt_prim& cp = s->prims[in.child];
-            if (cp.kind == RT_PRIM_MEDIUM) {
-                const rt_prim& b = s->prims[cp.a];
-                return b.kind == RT_PRIM_INSTANCE ? inst_moving(b.a) : moving(cp.a);
-            }
-            return moving(in.child);
-        };
-        bool nest = false;
-        for (int i = 0; i < s->n_instances && !nest; ++i) nest = inst_moving(i);
-        for (int i = 0; i < s->n_prims && !nest; ++i) {
-            if (s->prims[i].kind != RT_PRIM_MEDIUM) continue;
-            const int b = s->prims[i].a;
-            nest = s->prims[b].kind == RT_PRIM_INSTANCE ? inst_moving(s->prims[b].a) : moving(b);
-        }
-        if (nest) feat |= rtk::FEAT_NEST_MOVING;
-    }
-    c->features = feat;
-    c->S.has_lights = 0;   // any DiffuseLight: without one, a hit never emits (shade_begin skips its material read)
-    for (int i = 0; i < s->n_materials; ++i)
-        if (s->materials[i].kind == RT_MAT_DIFFUSE_LIGHT) c->S.has_lights = 1;
-    c->S.has_spheres = 0;
-    for (int i = 0; i < s->n_prims; ++i)
-        if (s->prims[i].kind == RT_PRIM_SPHERE || s->prims[i].kind == RT_PRIM_MOVING_SPHERE) c->S.has_spheres = 1;
-    c->pad_extent = s->pad_extent > 0.0 && std::isfinite(s->pad_extent) ? s->pad_extent : 0.0;
     c->stats.scene_bytes = (int64_t)total;
     return RT_OK;
 }

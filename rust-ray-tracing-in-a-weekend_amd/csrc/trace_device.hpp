@@ -702,7 +702,7 @@ __device__ __forceinline__ bool box_t(const rt_prim& p, const RayT<R>& r, R t_mi
 // The centre of a Sphere, or of a MovingSphere at the ray's time: center_0 +
 // ((time - time_0) / (time_1 - time_0)) * (center_1 - center_0) (hittable.rs:556-558).
 // Both kinds go through one code path with no select: the upload stores a Sphere as a
-// MovingSphere of velocity 0 (abi.cpp), whose c0 + 0 * s is c0 bit for bit (s finite), so
+// MovingSphere of velocity 0 (scene_lower.cpp), whose c0 + 0 * s is c0 bit for bit (s finite), so
 // a wave whose lanes hold both kinds runs one test and loads no kind.
 template <class R>
 __device__ __forceinline__ void sphere_center(const rt_prim& p, const RayT<R>& r, bool general, double& cx, double& cy,
@@ -1724,7 +1724,7 @@ __device__ __forceinline__ void stage_lds(const SceneDev& S)
         any = true;
     }
     if constexpr (StageBlas<C>()) {
-        if (S.n_lds_blas > 0) {   // the BLAS's BFS prefix, nodes[n_tlas_nodes, ...) (abi.cpp)
+        if (S.n_lds_blas > 0) {   // the BLAS's BFS prefix, nodes[n_tlas_nodes, ...) (scene_lower.cpp)
             uint4* db = reinterpret_cast<uint4*>(reinterpret_cast<char*>(rt_lds) + lds_layout_of<C>(S).blas);
             const uint4* sb = reinterpret_cast<const uint4*>(S.nodes + S.n_tlas_nodes);
             for (int i = threadIdx.x; i < S.n_lds_blas * 4; i += BlockThreads<C>()) db[i] = sb[i];
@@ -2651,7 +2651,7 @@ static void launch_f(const Launch& L, int slab32, int lds, hipStream_t stream)
     // whose node addresses or leaf codes do not fit takes the partial-TLAS instantiation
     constexpr bool S16F = F == FEAT_SET_SPHERES;   // Stack16Cfg's feature set
     if (RT_STACK16 && S16F && slab32 && lds && !S.stack16_ok) nall = false;
-    // stack16_ok (abi.cpp) assumes the node records start at LDS address 0, i.e. that rt_lds is
+    // stack16_ok (scene_lower.cpp) assumes the node records start at LDS address 0, i.e. that rt_lds is
     // the kernels' only __shared__ object: a static __shared__ variable would move the dynamic
     // base up, and 16-bit stack entries would truncate node addresses past 32 KB. Checked on the
     // compiled kernels: any static LDS in them sends the scene to the 32-bit-stack instantiation.

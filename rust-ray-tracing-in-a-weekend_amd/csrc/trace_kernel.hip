@@ -283,15 +283,6 @@ __global__ void eval_numerics(int fn, const double* x, const double* y, const do
 // ---------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------
-uint32_t variant_features(uint32_t scene_features)
-{
-    if ((scene_features & ~FEAT_SET_SPHERES) == 0) return FEAT_SET_SPHERES;
-    if ((scene_features & ~FEAT_SET_RECTINST) == 0) return FEAT_SET_RECTINST;
-    if ((scene_features & ~FEAT_SET_MEDIA) == 0) return FEAT_SET_MEDIA;
-    if ((scene_features & ~FEAT_SET_FINAL) == 0) return FEAT_SET_FINAL;
-    return FEAT_ALL;
-}
-
 hipError_t launch_trace(const SceneDev& S, const KParams& Ph, const KParams* P, double* out,
                         unsigned long long* counters, unsigned* work, const LaunchOpts& o, hipStream_t stream)
 {

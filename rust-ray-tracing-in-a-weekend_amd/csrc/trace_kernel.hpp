@@ -4,19 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include "rt/rt_scene.h"
-
-// The first instance a cast's top-level walk reaches is tested after that walk (trace_world's
-// DeferInst), its BLAS walk then starting at stack entry 0; shared with the host, which sizes the
-// stack from it (abi.cpp: a scene where no other nested walk can happen needs max(TLAS, BLAS)
-// entries instead of their sum)
-#ifndef RT_DEFER_INST
-#define RT_DEFER_INST 1
-#endif
+#include "scene_features.hpp"   // FEAT_*, variant_features, RT_DEFER_INST
 
 // Threads per workgroup of the final-scene variant's kernels (the others: 256). 512 (8 waves)
 // shares one LDS copy of the TLAS and materials among twice the waves, which leaves room for
 // the instanced BLAS in LDS (SceneDev.n_lds_blas; the host sizes that budget with it): the
-// final scene's 1000-sphere BLAS 512 of 548 nodes staged instead of 64, C4 1920x1080x100
+// final scene's 1000-sphere BLAS 512 of (then) 548 nodes staged instead of 64 (597 today), C4 1920x1080x100
 // 110.95 -> 108.23 ms; 512 threads with 64 staged 111.27 (profiles/r03r_ab_c4.log)
 // Round 6: 1024 (16 waves, one workgroup per CU at 4 waves per SIMD) stages the whole BLAS and
 // shares one copy of everything among the CU's waves: C4 1920x1080x1000 979.1 -> 976.4 ms, f32 mode
@@ -77,7 +70,7 @@ struct SceneDev {
     int32_t tlas_root;
     int32_t blas_base;      // first stack entry of a BLAS walk nested in the top-level walk
     int32_t stack_entries;  // traversal stack entries per lane (TLAS + nested BLAS walk, or the
-                            // larger of the two when every BLAS walk is a deferred one: abi.cpp)
+                            // larger of the two when every BLAS walk is a deferred one: scene_lower.cpp)
     int32_t n_lds_nodes;    // the first n TLAS nodes (BFS order, nodes[0, n)) are copied into LDS
     int32_t n_tlas_nodes;   // TLAS size (its nodes are nodes[0, n_tlas_nodes))
     int32_t has_spheres;    // any Sphere / MovingSphere: rays need 1/|d|^2 for the root divisions
@@ -98,7 +91,7 @@ struct SceneDev {
     int32_t stack16_ok;
     // BLAS nodes staged in LDS after the TLAS records (variants with instanced BLASes): the device
     // node array holds one instance BLAS's nodes in BFS order right after the TLAS prefix,
-    // nodes[n_tlas_nodes, n_tlas_nodes + n_blas_bfs) (abi.cpp), and a launch stages the first
+    // nodes[n_tlas_nodes, n_tlas_nodes + n_blas_bfs) (scene_lower.cpp), and a launch stages the first
     // n_lds_blas of them (its LDS budget): the nested walk's top levels then read LDS
     int32_t n_blas_bfs, n_lds_blas;
     int32_t pad0;           // (unused: keeps the kernel-argument layout the kernels were timed with)
@@ -158,31 +151,6 @@ constexpr int kRingSampleBits = 20;            // ring: samples below 2^20, the 
 constexpr uint32_t kRingSampleMask = (1u << kRingSampleBits) - 1;
 static_assert(kPoolRing * kRingSlot <= (1u << (32 - kRingSampleBits)), "ring record index bits");
 
-// Scene features (which code a kernel variant must contain).
-enum : uint32_t {
-    FEAT_RECT = 1,      // XY/XZ/YZ rects and boxes
-    FEAT_INST = 2,      // Translate / RotateY instances
-    FEAT_MEDIUM = 4,    // ConstantMedium
-    FEAT_NOISE = 8,     // Perlin noise texture
-    FEAT_IMAGE = 16,    // image texture
-    FEAT_INST_RECT = 32,    // rects or boxes inside an instance (its child prim or BLAS)
-    FEAT_MEDIUM_INST = 64,  // a medium boundary that is not a sphere (box, rect, instance)
-    FEAT_INST_MEDIUM = 128, // a medium inside an instance (nested Translate/RotateY over a ConstantMedium)
-    FEAT_INST_BLAS = 256,   // an instance over a BVH (a nested walk; instances over one primitive need none)
-    FEAT_SHUTTER = 512,     // a MovingSphere whose shutter is not [0, 1] (its centre needs a division)
-    FEAT_NEST_MOVING = 1024, // a MovingSphere (nonzero velocity) under an instance or in a medium boundary
-    FEAT_IMAGE_UV = 2048,    // an image texture on a rect / box or an instanced primitive (its uv is stored at
-                             // the hit; else it is a top-level sphere's, recomputed from the hit normal)
-    FEAT_ALL = 4095,
-    FEAT_STATIC = 1u << 16,  // kernel-internal (InstC / BoundC): every sphere reached here is static
-    FEAT_SET_SPHERES = 0,                                          // compiled variant: spheres + solid/checker
-    FEAT_SET_RECTINST = FEAT_RECT | FEAT_INST | FEAT_INST_RECT,    // + rects, boxes, instances of one prim (Cornell)
-    FEAT_SET_MEDIA = FEAT_SET_RECTINST | FEAT_MEDIUM | FEAT_MEDIUM_INST,  // + constant media (Cornell smoke)
-    // + Perlin and image textures, instances over spheres, media bounded by spheres (final scene)
-    FEAT_SET_FINAL = FEAT_RECT | FEAT_INST | FEAT_MEDIUM | FEAT_NOISE | FEAT_IMAGE | FEAT_INST_BLAS
-};
-static_assert(FEAT_SET_FINAL == 287u, "block_threads_of");
-
 struct LaunchOpts {
     uint32_t features;  // scene features (FEAT_*)
     int slab32;         // conservative f32 slab tests
@@ -214,7 +182,6 @@ __host__ __device__ inline size_t tiled_pixels(int width, int n_rows)   // recor
     return (size_t)((width + 7) / 8) * (size_t)((n_rows + 7) / 8) * 64;
 }
 
-uint32_t variant_features(uint32_t scene_features);
 // Ph: host copy of the params (grid size); P: the same params in device memory
 // chunk schedule: out = chunk partials [n_chunks][n_px][3]; pool schedule: out = per-sample
 // radiance, tiled_record order over spp - sample_begin samples; work = one device counter
