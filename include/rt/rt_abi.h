@@ -28,6 +28,8 @@
  *                             8x8 tile shards, one RCCL gather to rank 0, a reorder kernel
  *   rt_render_adaptive        (new) the same driver loop with the per-pixel sample count
  *                             (main.rs:516) decided per 8x8 tile from the estimate's noise
+ *   rt_denoise                (new) a post-filter over the adaptive frame and its noise map; the
+ *                             reference has no filter
  *
  * Threading: a context is bound to one device and is used by one host thread at
  * a time. Worlds are plain host objects.
@@ -472,6 +474,55 @@ int rt_adaptive_last_stats(rt_ctx* ctx, rt_adaptive_stats* out);
  * (either may be NULL). For callers with accumulators of their own, and for tests. */
 int rt_adaptive_tile_errors_host(const double* sums, const double* q, const uint32_t* tile_spp, int width,
                                  int height, double* tile_error_out, double* stderr_out);
+
+/* ---- variance-guided NL-means denoiser (additive to ABI v6: new symbols only) ------------------
+ * A post-filter for rt_render_adaptive's frame that needs only the colour and the per-pixel
+ * standard error the adaptive call already returns: non-local means with variance-normalised
+ * patch distances (Rousselle, Knaus, Zwicker 2012). No albedo, normal or depth buffer, no uploaded
+ * scene, no scratch buffer: it reads mean and stderr_map and writes out.
+ *
+ * The filter. Inputs: M, height x width x 3 mean radiance (f32 or f64, row 0 = bottom); se, height
+ * x width f64 (rt_adaptive_out.stderr_map); radius r in 1..10; patch f in 0..3; k > 0 and finite.
+ * All arithmetic is f64 with no contraction; f32 input is widened first.
+ *   Y(a)     = the luminance of M(a), by rt_render_adaptive's expression for Y
+ *   V(a)     = se(a)^2
+ * For a pixel a and an offset o in [-r, r]^2 the pair (a, o) is valid if a and a + o are both inside
+ * the image.
+ *   delta(a, o) = ((Y(a) - Y(a+o))^2 - (V(a) + min(V(a), V(a+o)))) / (1e-10 + k^2 (V(a) + V(a+o)))
+ *   D(p, o)     = the sum of delta(p+s, o) over the s in [-f, f]^2 whose pair (p+s, o) is valid,
+ *                 divided by the number of such s
+ *   w(p, o)     = exp(-max(0, D)) if D is finite, otherwise 0; w(p, (0,0)) = 1 by definition
+ *   out(p)      = sum_o w(p,o) M(p+o) / sum_o w(p,o) over the offsets with p + o inside the image,
+ *                 taken in raster order (dy outer, dx inner); terms with w = 0 are skipped, not
+ *                 multiplied
+ * If Y(p) or V(p) is not finite, out(p) = M(p): with the finite-D rule a NaN or Inf pixel stays
+ * where it is and does not spread. out has M's format; an f32 out is the f64 result rounded once.
+ * The patch sums are direct sums of their (2f+1)^2 terms (no running sums or integral images:
+ * where V = 0, delta reaches 1e10 and a running sum loses the small terms next to it). The distance
+ * is not symmetric in (a, a+o). Nothing depends on the device's tiling: the result repeats bit for
+ * bit, and the device and host filters differ only by their exp (an ulp of a weight). */
+typedef struct rt_denoise_params {
+    int32_t width, height;
+    int32_t format;      /* RT_OUT_F32 / RT_OUT_F64, of mean and out */
+    int32_t on_device;   /* 0: host pointers, synchronous; 1: device pointers, only enqueued */
+    int32_t radius, patch;
+    double k;
+    void* stream;        /* hipStream_t (NULL = the context's stream) */
+} rt_denoise_params;
+/* RT_ERR_INVALID: a null pointer, out == mean, a bad format, width or height < 1, radius, patch or
+ * k out of range. Needs no uploaded scene. With on_device set, rt_render_adaptive with
+ * out_on_device followed by rt_denoise on the same stream runs with no host round trip. */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* p, const void* mean, const double* stderr_map, void* out);
+/* The same filter on the host, no device needed (on_device and stream are ignored). */
+int rt_denoise_host(const rt_denoise_params* p, const void* mean, const double* stderr_map, void* out);
+
+typedef struct rt_denoise_stats {
+    double kernel_ms;        /* last rt_denoise: the filter kernel (HIP events; waits for it if only enqueued) */
+    int32_t radius, patch;
+    int32_t lds_bytes;       /* LDS of one workgroup (one 16x16 tile) */
+    int32_t reserved0;
+} rt_denoise_stats;
+int rt_denoise_last_stats(rt_ctx* ctx, rt_denoise_stats* out);
 
 /* ---- output ------------------------------------------------------------------------------ */
 /* P3 PPM byte for byte as the reference writes it (write_color, math.rs:119-132; main.rs:472,

@@ -16,6 +16,7 @@
 #include "rt/rt_abi.h"
 #include "adaptive_criterion.hpp"
 #include "ctx_internal.hpp"
+#include "denoise.hpp"
 #include "scene_lower.hpp"
 #include "scene_model.hpp"
 #include "trace_kernel.hpp"
@@ -102,6 +103,9 @@ struct rt_ctx {
     bool pending_counts = false;
     rt_stats stats{};
     rt_adaptive_stats astats{};         // the last rt_render_adaptive (rt_adaptive_last_stats)
+    rt_denoise_stats dstats{};          // the last rt_denoise (rt_denoise_last_stats)
+    hipEvent_t ev_dn[2] = {nullptr, nullptr};   // around its kernel
+    bool pending_dn = false;            // its kernel_ms is still to be read from the events
     uint32_t features = rtk::FEAT_ALL;  // of the uploaded scene
     int n_materials = 0, n_textures = 0;
     int block_chunks = 0;               // RT_OPT_BLOCK_CHUNKS: chunks per item-pool work block (0: auto)
@@ -211,6 +215,7 @@ int rt_ctx_create(int device, rt_ctx** out)
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->ev_tr[i], hipEventDisableTiming);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->ev_rd[i], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev_dn[i]);
     if (e != hipSuccess) {
         rt_ctx_destroy(c);
         return hip_fail(e, "rt_ctx_create");
@@ -245,6 +250,8 @@ void rt_ctx_destroy(rt_ctx* c)
         if (c->ev_rd[i]) (void)hipEventDestroy(c->ev_rd[i]);
     }
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
+    for (auto& e : c->ev_dn)
+        if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1519,6 +1526,71 @@ int rt_adaptive_last_stats(rt_ctx* c, rt_adaptive_stats* out)
 {
     if (!c || !out) return fail(RT_ERR_INVALID, "null argument");
     *out = c->astats;
+    return RT_OK;
+}
+
+// ---- variance-guided NL-means (rt_abi.h: the filter; denoise_kernel.hip; denoise_host.cpp) -------
+namespace {
+// rt_denoise_host lives in denoise_host.cpp, which links without this file: its error text comes
+// through a hook
+[[maybe_unused]] const bool g_denoise_sink_set =(rtk::denoise_error_sink = [](const char* msg) { g_last_error = msg; }, true);
+}  // namespace
+
+int rt_denoise(rt_ctx* c, const rt_denoise_params* p, const void* mean, const double* stderr_map, void* out)
+{
+    if (!c) return fail(RT_ERR_INVALID, "null argument");
+    if (const char* bad = rtk::denoise_check(p, mean, stderr_map, out)) return fail(RT_ERR_INVALID, bad);
+    const bool f64 = p->format == RT_OUT_F64, on_dev = p->on_device != 0;
+    const size_t hw = (size_t)p->width * (size_t)p->height;
+    const size_t frame_bytes = hw * 3 * (f64 ? 8 : 4), se_bytes = hw * sizeof(double);
+
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = p->stream ? (hipStream_t)p->stream : c->stream;
+    StreamScope scope(c, stream);
+    int rc = scope.begin();
+    if (rc) return rc;
+
+    // host pointers: the frame, the map and the result staged in one device block of the call's own
+    DeviceBlock blk;
+    const void* d_mean = mean;
+    const double* d_se = stderr_map;
+    void* d_out = out;
+    if (!on_dev) {
+        const size_t off_se = align_up(frame_bytes, 256), off_out = off_se + align_up(se_bytes, 256);
+        HIP_TRY(hipMalloc(&blk.p, off_out + frame_bytes));
+        d_mean = blk.p;
+        d_se = (const double*)((char*)blk.p + off_se);
+        d_out = (char*)blk.p + off_out;
+        HIP_TRY(hipMemcpyAsync(blk.p, mean, frame_bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync((void*)d_se, stderr_map, se_bytes, hipMemcpyHostToDevice, stream));
+    }
+    HIP_TRY(hipEventRecord(c->ev_dn[0], stream));
+    HIP_TRY(rtk::launch_denoise(d_mean, d_se, d_out, f64, p->width, p->height, p->radius, p->patch, p->k, stream));
+    HIP_TRY(hipEventRecord(c->ev_dn[1], stream));
+    c->dstats = rt_denoise_stats{};
+    c->dstats.radius = p->radius;
+    c->dstats.patch = p->patch;
+    c->dstats.lds_bytes = rtk::denoise_lds_bytes(p->radius, p->patch);
+    c->pending_dn = true;
+    if (!on_dev) HIP_TRY(hipMemcpyAsync(out, d_out, frame_bytes, hipMemcpyDeviceToHost, stream));
+    rc = scope.end();
+    if (rc) return rc;
+    if (!on_dev) HIP_TRY(hipStreamSynchronize(stream));   // (the block is freed once its copies are done)
+    return RT_OK;
+}
+
+int rt_denoise_last_stats(rt_ctx* c, rt_denoise_stats* out)
+{
+    if (!c || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (c->pending_dn) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipEventSynchronize(c->ev_dn[1]));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_dn[0], c->ev_dn[1]));
+        c->dstats.kernel_ms = ms;
+        c->pending_dn = false;
+    }
+    *out = c->dstats;
     return RT_OK;
 }
 

@@ -79,6 +79,7 @@ EXPORTED = [
     "rt_comm_tile_order", "rt_comm_tile_order_all", "rt_render_gather", "rt_render_gather_all",
     "rt_comm_last_stats", "rt_tiles_assemble", "rt_tiles_assemble_host", "rt_cost_tile_order",
     "rt_render_adaptive", "rt_adaptive_last_stats", "rt_adaptive_tile_errors_host",
+    "rt_denoise", "rt_denoise_host", "rt_denoise_last_stats",
 ]
 
 # int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_total)
@@ -187,6 +188,22 @@ class AdaptiveStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DenoiseParams(ctypes.Structure):
+    """rt_denoise_params."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("format", ctypes.c_int32),
+                ("on_device", ctypes.c_int32), ("radius", ctypes.c_int32), ("patch", ctypes.c_int32),
+                ("k", ctypes.c_double), ("stream", ctypes.c_void_p)]
+
+
+class DenoiseStats(ctypes.Structure):
+    """rt_denoise_stats: the last rt_denoise of a context."""
+    _fields_ = [("kernel_ms", ctypes.c_double), ("radius", ctypes.c_int32), ("patch", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -260,6 +277,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                 ctypes.POINTER(AdaptiveParams), ctypes.POINTER(AdaptiveOut)], I),
         "rt_adaptive_last_stats": ([P, ctypes.POINTER(AdaptiveStats)], I),
         "rt_adaptive_tile_errors_host": ([P, P, P, I, I, P, P], I),
+        "rt_denoise": ([P, ctypes.POINTER(DenoiseParams), P, P, P], I),
+        "rt_denoise_host": ([ctypes.POINTER(DenoiseParams), P, P, P], I),
+        "rt_denoise_last_stats": ([P, ctypes.POINTER(DenoiseStats)], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name, None)
@@ -576,6 +596,31 @@ def adaptive_tile_errors_host(sums, q, tile_spp, width: int, height: int):
     return err, se
 
 
+def _denoise_args(mean, se, radius, patch, k):
+    """(params, mean, se) of a host-pointer denoise call: mean height x width x 3 f32 or f64 (its
+    dtype is the format), se height x width."""
+    m = np.asarray(mean)
+    if m.ndim != 3 or m.shape[2] != 3:
+        raise RTError(f"denoise: mean is {m.shape}, not height x width x 3")
+    m = np.ascontiguousarray(m, dtype=np.float32 if m.dtype == np.float32 else np.float64)
+    s = np.ascontiguousarray(se, dtype=np.float64)
+    if s.shape != m.shape[:2]:
+        raise RTError(f"denoise: the error map is {s.shape}, the frame {m.shape[:2]}")
+    fmt = RT_OUT_F64 if m.dtype == np.float64 else RT_OUT_F32
+    return DenoiseParams(m.shape[1], m.shape[0], fmt, 0, int(radius), int(patch), float(k), None), m, s
+
+
+def denoise_host(mean, se, radius: int = 10, patch: int = 3, k: float = 0.45) -> np.ndarray:
+    """rt_denoise_host: the variance-guided NL-means filter (rt_abi.h) on the host, no device needed.
+    mean: height x width x 3 f32 or f64, se: height x width (render_adaptive's stderr_map).
+    Returns the filtered frame in mean's format."""
+    lib = load_library()
+    p, m, s = _denoise_args(mean, se, radius, patch, k)
+    out = np.empty_like(m)
+    _check(lib.rt_denoise_host(ctypes.byref(p), m.ctypes.data, s.ctypes.data, out.ctypes.data), "rt_denoise_host")
+    return out
+
+
 def write_ppm(rgb: np.ndarray, path: str, samples_per_pixel: int = 1) -> None:
     """P3 writer of the reference (write_color, math.rs:119-132; main.rs:472, 591-596):
     height x width x 3, row 0 = bottom. An f64 array takes rt_write_ppm_f64 — the reference's
@@ -693,6 +738,42 @@ class Renderer:
         _check(self.lib.rt_render_adaptive(self.h, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(ap),
                                            ctypes.byref(out)), "rt_render_adaptive")
         return mean, tile_spp, tile_error, se
+
+    def render_adaptive_device(self, camera: Camera, params: RenderParams, min_spp: int, step_spp: int,
+                               threshold: float, mean_ptr: int, stderr_ptr: int = 0, tile_spp_ptr: int = 0,
+                               tile_error_ptr: int = 0, stream: Optional[int] = None):
+        """rt_render_adaptive into device buffers (e.g. torch tensors' data_ptr()): mean height x
+        width x 3 of params.out_format, the optional others as rt_adaptive_out. The call itself is
+        synchronous."""
+        params.out_on_device = 1
+        params.stream = stream
+        ap = AdaptiveParams(int(min_spp), int(step_spp), float(threshold))
+        out = AdaptiveOut(mean_ptr, tile_spp_ptr or None, tile_error_ptr or None, stderr_ptr or None)
+        _check(self.lib.rt_render_adaptive(self.h, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(ap),
+                                           ctypes.byref(out)), "rt_render_adaptive")
+
+    def denoise(self, mean, se, radius: int = 10, patch: int = 3, k: float = 0.45) -> np.ndarray:
+        """rt_denoise on host arrays (synchronous): mean height x width x 3 f32 or f64, se height x
+        width, as render_adaptive returns them. Returns the filtered frame in mean's format."""
+        p, m, s = _denoise_args(mean, se, radius, patch, k)
+        out = np.empty_like(m)
+        _check(self.lib.rt_denoise(self.h, ctypes.byref(p), m.ctypes.data, s.ctypes.data, out.ctypes.data),
+               "rt_denoise")
+        return out
+
+    def denoise_device(self, mean_ptr: int, stderr_ptr: int, out_ptr: int, width: int, height: int,
+                       out_format: int = RT_OUT_F32, radius: int = 10, patch: int = 3, k: float = 0.45,
+                       stream: Optional[int] = None):
+        """Enqueues rt_denoise over device buffers (mean and out height x width x 3 of out_format,
+        the error map height x width f64) on `stream`."""
+        p = DenoiseParams(int(width), int(height), int(out_format), 1, int(radius), int(patch), float(k), stream)
+        _check(self.lib.rt_denoise(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr), ctypes.c_void_p(stderr_ptr),
+                                   ctypes.c_void_p(out_ptr)), "rt_denoise")
+
+    def denoise_stats(self) -> DenoiseStats:
+        s = DenoiseStats()
+        _check(self.lib.rt_denoise_last_stats(self.h, ctypes.byref(s)), "rt_denoise_last_stats")
+        return s
 
     def adaptive_stats(self) -> AdaptiveStats:
         s = AdaptiveStats()

@@ -14,9 +14,14 @@ in a stream synchronise), and the HIP-event times the library reports. Bytes/s o
 the per-sample records they read (24 B x samples traced) over their event time.
 Error: RMSE of sqrt(clamp(mean, 0, 0.999)) (the output's gamma) against a uniform render at
 --ref-mult x spp under another render seed, so the reference shares no sample with either frame.
+--denoise R F K: every mode's frame also goes through rt_denoise (radius R, patch F, k K) with the
+error map of its own adaptive call (the uniform frame: of an adaptive call at threshold 0, which
+renders the same frame); reported are rmse_denoised beside rmse, the filter kernel's HIP-event time
+and the wall time of the host-pointer call (copies included). Without it the output is unchanged.
 
 usage: python scripts/adaptive_bench.py --config C2 --thresholds 0.02 0.01 0.005 \
-           [--parent lib/librtiow_parent.so] [--min-spp 64 --step-spp 64] [--out adaptive_c2.json]
+           [--parent lib/librtiow_parent.so] [--min-spp 64 --step-spp 64] [--denoise 10 3 0.45]
+           [--out adaptive_c2.json]
 """
 import argparse
 import json
@@ -52,6 +57,20 @@ if a["ref"]:
         np.save(a["ref"], r.render(cam, p))
     ref = gamma(np.load(a["ref"]))
 res = {{}}
+dn = a.get("denoise")
+uniform_se = []
+def denoised(mode, img, se, d):
+    if mode == "uniform":
+        if not uniform_se:   # the same frame's error map: an adaptive call that never stops early
+            p = rt.Renderer.params(W, H, spp, a["depth"], bg, 1, out_format=rt.RT_OUT_F32)
+            uniform_se.append(r.render_adaptive(cam, p, a["min_spp"], a["step_spp"], 0.0)[3])
+        se = uniform_se[0]
+    t0 = time.perf_counter()
+    out = r.denoise(img, se, int(dn[0]), int(dn[1]), float(dn[2]))
+    d["denoise_wall_ms"] = (time.perf_counter() - t0) * 1e3
+    st = r.denoise_stats()
+    d.update(denoise_kernel_ms=st.kernel_ms, denoise_lds_bytes=st.lds_bytes)
+    return out
 def run(mode):
     p = rt.Renderer.params(W, H, spp, a["depth"], bg, 1, out_format=rt.RT_OUT_F32)
     t0 = time.perf_counter()
@@ -59,8 +78,8 @@ def run(mode):
         img = r.render(cam, p)
         ms = (time.perf_counter() - t0) * 1e3
         st = r.stats()
-        return img, dict(wall_ms=ms, trace_ms=st.kernel_ms, reduce_ms=st.reduce_ms, samples=st.samples,
-                         schedule=st.schedule, n_batches=st.n_batches)
+        return img, None, dict(wall_ms=ms, trace_ms=st.kernel_ms, reduce_ms=st.reduce_ms, samples=st.samples,
+                               schedule=st.schedule, n_batches=st.n_batches)
     img, tile_spp, tile_err, se = r.render_adaptive(cam, p, a["min_spp"], a["step_spp"], float(mode))
     ms = (time.perf_counter() - t0) * 1e3
     st = r.adaptive_stats()
@@ -68,16 +87,21 @@ def run(mode):
     d.update(wall_ms=ms, reduce_ms=st.moments_ms, samples=st.samples_traced, mean_tile_spp=float(tile_spp.mean()),
              tiles_at_max=int((tile_spp == spp).sum()), tiles_at_min=int((tile_spp == st.min_spp).sum()),
              tile_error_pct=[float(x) for x in np.percentile(tile_err, [5, 25, 50, 75, 95, 100])])
-    return img, d
+    return img, se, d
 for mode in a["modes"]:
-    run(mode)                                  # warm-up: code objects, buffers
+    img, se, d = run(mode)                     # warm-up: code objects, buffers
+    if dn:
+        denoised(mode, img, se, d)
 for _ in range(a["reps"]):
     for mode in a["modes"]:
-        img, d = run(mode)
+        img, se, d = run(mode)
+        out = denoised(mode, img, se, d) if dn else None
         e = res.setdefault(mode, dict(runs=[]))
         e["runs"].append(d)
         if ref is not None and "rmse" not in e:
             e["rmse"] = float(np.sqrt(np.mean((gamma(img) - ref) ** 2)))
+            if dn:
+                e["rmse_denoised"] = float(np.sqrt(np.mean((gamma(out) - ref) ** 2)))
 print("RESULT", json.dumps(res))
 """
 
@@ -98,6 +122,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ref-mult", type=int, default=4, help="the error reference: uniform at this many x spp (0: none)")
+    ap.add_argument("--denoise", type=float, nargs=3, default=None, metavar=("R", "F", "K"),
+                    help="also filter every frame with rt_denoise: radius, patch, k")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     cfg = CONFIGS[a.config]
@@ -111,6 +137,8 @@ def main():
         for name, lib, modes in jobs:
             args = dict(cfg, modes=modes, reps=a.reps, min_spp=a.min_spp, step_spp=a.step_spp, ref=ref,
                         ref_mult=a.ref_mult)
+            if a.denoise and name == "new":
+                args["denoise"] = a.denoise
             env = dict(os.environ, RT_LIB_PATH=os.path.abspath(os.path.join(REPO, lib)))
             out = subprocess.run([sys.executable, "-c", CHILD.format(repo=REPO, args=json.dumps(args))], env=env,
                                  capture_output=True, text=True, timeout=900)
@@ -119,7 +147,7 @@ def main():
                 sys.exit(out.returncode if out.returncode > 0 else 1)
             d = json.loads([x for x in out.stdout.splitlines() if x.startswith("RESULT ")][-1][7:])
             for mode, e in d.items():
-                k = runs.setdefault(f"{name}:{mode}", dict(runs=[], rmse=e.get("rmse")))
+                k = runs.setdefault(f"{name}:{mode}", dict(runs=[], rmse=e.get("rmse"), rmse_denoised=e.get("rmse_denoised")))
                 k["runs"] += e["runs"]
                 print(f"  {name}:{mode}: wall {['%.2f' % x['wall_ms'] for x in e['runs']]}", flush=True)
     uniform_px = cfg["width"] * cfg["height"] * cfg["spp"]
@@ -135,6 +163,10 @@ def main():
                  reduce_GBps=rs[0]["samples"] * 24 / red / 1e6 if red > 0 else None, rmse=e["rmse"])
         if "tile_error_pct" in rs[0]:
             s["tile_error_pct_5_25_50_75_95_100"] = rs[0]["tile_error_pct"]
+        if "denoise_kernel_ms" in rs[0]:
+            s.update(rmse_denoised=e["rmse_denoised"], denoise_kernel_ms=median([x["denoise_kernel_ms"] for x in rs]),
+                     denoise_wall_ms=median([x["denoise_wall_ms"] for x in rs]), denoise_lds_bytes=rs[0]["denoise_lds_bytes"],
+                     denoise_kernel_over_wall=median([x["denoise_kernel_ms"] for x in rs]) / median(wall))
         for k in ("passes", "classify_ms", "mean_tile_spp", "tiles_at_max", "tiles_at_min", "tiles", "schedule", "n_batches",
                   "max_pass_batches"):
             if k in rs[0]:
@@ -142,8 +174,10 @@ def main():
         summary[key] = s
         print(f"{a.config} {key}: " + json.dumps(s))
     if a.out:
-        json.dump(dict(config=a.config, params=cfg, min_spp=a.min_spp, step_spp=a.step_spp, base_wall_ms=base,
-                       results=summary), open(a.out, "w"), indent=1)
+        doc = dict(config=a.config, params=cfg, min_spp=a.min_spp, step_spp=a.step_spp, base_wall_ms=base, results=summary)
+        if a.denoise:
+            doc["denoise"] = a.denoise
+        json.dump(doc, open(a.out, "w"), indent=1)
 
 
 if __name__ == "__main__":
