@@ -17,6 +17,7 @@
 #include "adaptive_criterion.hpp"
 #include "ctx_internal.hpp"
 #include "denoise.hpp"
+#include "launch_plan.hpp"
 #include "scene_lower.hpp"
 #include "scene_model.hpp"
 #include "trace_kernel.hpp"
@@ -47,26 +48,6 @@ size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // device slots for launch params (a ring: a render's params stay intact while later
 // renders are enqueued behind it on the same stream)
 constexpr int kParamSlots = 16;
-
-// LDS stack entries per lane above which the scratch stack is used (48 KB per block)
-constexpr int kMaxLdsStack = 48;
-// TLAS nodes kept in LDS (32 KB per block): the first kMaxLdsNodes in BFS order, i.e.
-// the top levels; deeper ones are read from L1/L2
-constexpr int kMaxLdsNodes = 512;
-// waves per SIMD of the final-scene variant (trace_device.hpp min_waves: its LDS budget is per
-// workgroup of the workgroups those waves make)
-#ifndef RT_MIN_WAVES_FINAL
-#define RT_MIN_WAVES_FINAL 4
-#endif
-// instance BLAS nodes staged in LDS at most (64 B each)
-#ifndef RT_LDS_BLAS_MAX
-#define RT_LDS_BLAS_MAX 1024   // the LDS budget decides (512-thread final variant: 512 of the final scene's then 548
-                               // BLAS nodes, 110.95 -> 108.23 ms at C4 1920x1080x100, r03r_ab_c4.log; with 256-thread
-                               // workgroups the budget held ~95: 64 staged 132.15 ms, 16 133.31, none 132.98, r03h)
-#endif
-constexpr int kMaxLdsBlas = RT_LDS_BLAS_MAX;
-// material (64 B) and texture (96 B) tables staged in LDS when both are this small (10 KB)
-constexpr int kMaxLdsMaterials = 64;
 
 }  // namespace
 
@@ -106,14 +87,12 @@ struct rt_ctx {
     rt_denoise_stats dstats{};          // the last rt_denoise (rt_denoise_last_stats)
     hipEvent_t ev_dn[2] = {nullptr, nullptr};   // around its kernel
     bool pending_dn = false;            // its kernel_ms is still to be read from the events
-    uint32_t features = rtk::FEAT_ALL;  // of the uploaded scene
-    int n_materials = 0, n_textures = 0;
-    int block_chunks = 0;               // RT_OPT_BLOCK_CHUNKS: chunks per item-pool work block (0: auto)
-    int block_samples = 0;              // RT_OPT_BLOCK_SAMPLES: samples per per-sample-pool work block (0: auto)
-    int opt_ring = 1;                   // RT_OPT_POOL_RING: POOL reduces finished blocks in the kernel (0 never,
-                                        // 1 when its per-sample buffer would not fit the bound, 2 always)
+    // what a render's launch plan is made from (launch_plan.hpp): the uploaded scene, the device, the switches
+    rtp::SceneFacts scene;
+    rtp::DeviceFacts dev;
+    rtp::Options opt;
     int opt_comm_direct = 1;            // RT_OPT_COMM_DIRECT: a world-1 rt_render_gather renders straight into the frame
-    double* ring = nullptr;             // its per-wave record ring (kPoolRing blocks per wave)
+    double* ring = nullptr;             // RT_OPT_POOL_RING's per-wave record rings (kPoolRing blocks per wave)
     size_t ring_cap = 0;
     unsigned long long raw_counters[kCounters] = {};   // the last count_work render's counters (rt_last_counters)
     uint32_t* tile_order = nullptr;     // rt_ctx_set_tile_order: tile shards' position -> raster tile (device)
@@ -121,28 +100,15 @@ struct rt_ctx {
     unsigned long long* tile_cost = nullptr;   // count_work pool renders: lane-cycles per raster tile
     int64_t tile_cost_cap = 0;          //   tiles allocated
     int64_t tile_cost_n = 0;            //   tiles of the last count_work render (rt_last_tile_costs)
-    uint32_t extra_features = 0;        // RT_OPT_EXTRA_FEATURES: a larger kernel variant than the scene needs (tests)
-    double pad_extent = 0.0;
-    int opt_slab32 = 1;                 // rt_ctx_set_variant
-    int opt_lds = 1;                    // rt_ctx_set_variant
-    int opt_lds_nodes = 1;              // rt_ctx_set_variant: keep the TLAS in LDS when it fits
     int opt_hoist = 1;                  // RT_OPT_HOIST: test a huge root-child leaf before the walk (pre_leaf)
-    int opt_pool = RT_SCHED_AUTO;       // rt_ctx_set_schedule: RT_SCHED_*
-    int opt_precision = RT_PREC_F64;    // rt_ctx_set_precision: RT_PREC_*
     size_t sample_buf_cap = (size_t)32 << 30;  // RT_OPT_TRACE_BUF_BYTES: bound of the trace-output buffer
     unsigned* work = nullptr;           // pool / item schedules: work-block counters (one per overlapped batch)
     // Overlapped buffer batches (RT_OPT_BATCH_OVERLAP): batch k traces on tstream[k & 1] into half k & 1
     // of the trace-output buffer while the caller's stream reduces batch k - 1
     hipStream_t tstream[2] = {nullptr, nullptr};
     hipEvent_t ev_in = nullptr, ev_tr[2] = {nullptr, nullptr}, ev_rd[2] = {nullptr, nullptr};
-    int opt_overlap = 1;
     double* acc_tmp = nullptr;          // running sums when a render takes several buffer batches
     size_t acc_tmp_cap = 0;
-    int n_tlas_nodes = 0;
-    int n_nodes = 0;                    // BVH nodes of the uploaded scene (TLAS + BLASes)
-    int n_cus = 256;
-    size_t lds_per_cu = 160 * 1024;     // the device's LDS per CU and per workgroup (read at creation)
-    size_t lds_per_block = 160 * 1024;
 };
 
 // The trace-output buffer's default bound: 64 GiB, or half the device's free memory if that is
@@ -198,12 +164,12 @@ int rt_ctx_create(int device, rt_ctx** out)
     {
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) == hipSuccess && v > 0)
-            c->lds_per_cu = (size_t)v;
+            c->dev.lds_per_cu = (size_t)v;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v > 0)
-            c->lds_per_block = (size_t)v;
+            c->dev.lds_per_block = (size_t)v;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0)
-            c->n_cus = v;
-        c->lds_per_block = std::min(c->lds_per_block, c->lds_per_cu);
+            c->dev.n_cus = v;
+        c->dev.lds_per_block = std::min(c->dev.lds_per_block, c->dev.lds_per_cu);
     }
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev[i]);
@@ -609,12 +575,7 @@ int rt_ctx_upload_soa(rt_ctx* c, const rt_scene_soa* s)
     S.n_lds_nodes = S.n_lds_blas = 0;   // a launch decides what it stages in LDS
     S.has_lights = L.has_lights;
     S.has_spheres = L.has_spheres;
-    c->n_tlas_nodes = L.n_tlas_nodes;
-    c->n_nodes = s->n_nodes;
-    c->n_materials = s->n_materials;
-    c->n_textures = s->n_textures;
-    c->features = L.features;
-    c->pad_extent = L.pad_extent;
+    c->scene = rtp::scene_facts(L, *s);
     c->has_scene = true;
     c->stats.scene_bytes = (int64_t)total;
     return RT_OK;
@@ -629,62 +590,21 @@ int rt_ctx_upload_world(rt_ctx* c, rt_world* w, int accel)
 }
 
 // ---- render ----------------------------------------------------------------------------
-int rt_rows_in_shard(int height, int row_begin, int row_stride)
-{
-    if (height <= 0 || row_stride <= 0 || row_begin < 0 || row_begin >= height) return 0;
-    return (height - row_begin + row_stride - 1) / row_stride;
-}
-
-// ceil(spp/16), at most 16 samples per work block (measured, pool schedule: C2 16 vs 32
-// 99.4 / 100.4 ms, C4 16 vs 63 1565 / 1636 ms, C3 flat); a function of spp only, so the
-// summation order (and the image) does not depend on launch geometry or sharding
-static int auto_chunk(int spp) { return std::min(16, std::max(1, (spp + 15) / 16)); }
-
+// (the shard geometry itself: launch_plan.cpp)
+int rt_rows_in_shard(int height, int row_begin, int row_stride) { return rtp::rows_in_shard(height, row_begin, row_stride); }
 int rt_rows_in_band_shard(int height, int row_begin, int row_stride, int row_block)
 {
-    if (row_block <= 1) return rt_rows_in_shard(height, row_begin, row_stride);
-    if (height <= 0 || row_stride <= 0 || row_begin < 0 || (row_block & (row_block - 1)) || row_block > 64) return 0;
-    const int bands = (height + row_block - 1) / row_block;
-    const int mine = rt_rows_in_shard(bands, row_begin, row_stride);
-    if (!mine) return 0;
-    const int last = row_begin + (mine - 1) * row_stride;   // its last band may be cut by the image
-    return (mine - 1) * row_block + std::min(row_block, height - last * row_block);
+    return rtp::rows_in_band_shard(height, row_begin, row_stride, row_block);
 }
-
 int rt_tiles_in_shard(int width, int height, int tile_begin, int tile_stride)
 {
-    if (width <= 0 || height <= 0) return 0;
-    const long long tiles = (long long)((width + 7) / 8) * ((height + 7) / 8);
-    if (tiles > 0x7fffffffLL) return 0;
-    return rt_rows_in_shard((int)tiles, tile_begin, tile_stride);
+    return rtp::tiles_in_shard(width, height, tile_begin, tile_stride);
 }
-
-static int row_block_of(const rt_render_params* p) { return p->row_block > 1 ? p->row_block : 1; }
-static int shard_rows(const rt_render_params* p)
-{
-    return rt_rows_in_band_shard(p->height, p->row_begin, p->row_stride, row_block_of(p));
-}
-// The shard's output layout (the kernel's pixel grid): its rows of the image, or (tile_shard)
-// its 8x8 tiles side by side in one 8-row slab
-struct Layout {
-    int w, rows;
-};
-static Layout layout_of(const rt_render_params* p)
-{
-    if (p->tile_shard) {
-        const int n = rt_tiles_in_shard(p->width, p->height, p->row_begin, p->row_stride);
-        return Layout{8 * n, n > 0 ? 8 : 0};
-    }
-    return Layout{p->width, shard_rows(p)};
-}
-
-static bool bad_geometry(const rt_render_params* p)
-{
-    const int b = row_block_of(p);
-    return p->width < 2 || p->height < 2 || p->row_stride < 1 || p->row_begin < 0 || p->spp_chunk < 0 ||
-           (b & (b - 1)) || b > 64 || (long long)p->width * p->height > 0xffffffffLL ||
-           (p->tile_shard != 0 && (p->tile_shard != 1 || b > 1));
-}
+using rtp::auto_chunk;
+using rtp::bad_geometry;
+using rtp::Layout;
+using rtp::layout_of;
+using rtp::row_block_of;
 
 static int grow(rt_ctx* c, hipStream_t stream, double*& buf, size_t& cap, size_t need, bool* oom = nullptr)
 {
@@ -720,39 +640,11 @@ struct Sink {
     int n_done = 0;
 };
 
-// Traces samples [s_begin, s_end) of the shard in chunks of `chunk` and reduces them into
-// the sink. Events: ev[0] before the first trace launch, ev[1] after the last one, ev[2]
-// after the last reduction. Chunk and item schedules: chunk partials per launch, reduced in
-// chunk order (or added to the sink's / a running accumulator across buffer batches).
-// Per-sample pool: per-sample radiance in batches; with more than one batch (or an acc
-// sink) the sums run through an accumulator plus the open chunk's sum (carried across
-// batches), which keeps the additions in the one-batch order.
-static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_begin, int s_end, int chunk,
-                     hipStream_t stream, const Sink& sink)
+// The launch params of a sample range, all but what the plan and the batch loop set (block sizes,
+// ring, sample range, work blocks). Fails on a context tile order that is not the frame's.
+static int fill_kparams(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const Layout& lay, int chunk,
+                        const Sink& sink, int64_t img_tiles, rtk::KParams& K)
 {
-    const Layout lay = layout_of(p);
-    const int n_rows = lay.rows;
-    const long long n_px = (long long)n_rows * lay.w;
-    const size_t px = (size_t)std::max<long long>(n_px, 1);
-    if (n_px == 0 || s_end <= s_begin) {
-        // an empty shard (rt_rows_in_shard / rt_tiles_in_shard 0: a rank past the tile count)
-        // or an empty sample range: nothing to trace or write; the events still bracket the
-        // (empty) work so rt_last_stats resolves
-        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventRecord(c->ev[i], stream));
-        c->stats.n_batches = 0;
-        c->stats.trace_buf_bytes = 0;
-        c->stats.overlapped = 0;
-        c->stats.ring_bytes = 0;
-        c->stats.samples = 0;
-        c->stats.n_items = 0;
-        c->stats.n_chunks = 0;
-        c->stats.spp_chunk = chunk;
-        c->pending_stats = true;
-        c->pending_counts = false;
-        return RT_OK;
-    }
-
-    rtk::KParams K;
     std::memset(&K, 0, sizeof K);
     K.cam = *cam;
     for (int i = 0; i < 3; ++i) K.bg[i] = p->background[i];
@@ -774,7 +666,6 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
     while ((1 << K.row_block_shift) < row_block_of(p)) K.row_block_shift++;
     K.tile_shard = p->tile_shard;
     K.img_tiles_x = (p->width + 7) / 8;
-    const int64_t img_tiles = (int64_t)K.img_tiles_x * ((p->height + 7) / 8);
     {   // t / img_tiles_x by multiply-high: m = floor(2^32 / d) + 1 gives floor(t * m / 2^32) =
         // floor(t / d) whenever t * (m d - 2^32) < 2^32 (the excess stays under one step of t / d)
         const uint64_t d = (uint64_t)K.img_tiles_x, m = ((uint64_t)1 << 32) / std::max<uint64_t>(d, 1) + 1;
@@ -791,203 +682,122 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
         K.tile_order = c->tile_order;
         K.tile_major = 1;   // the order's first tiles done first and entirely (rt_abi.h rt_ctx_set_tile_order)
     }
-    K.n_rows = n_rows;
+    K.n_rows = lay.rows;
     K.tiles_x = (lay.w + 7) / 8;
-    K.tiles_y = (n_rows + 7) / 8;
+    K.tiles_y = (lay.rows + 7) / 8;
+    return RT_OK;
+}
 
-    const bool count = p->count_work != 0;
-    // conservative f32 slab tests need every ray origin within 2M of the origin (flatten.cpp):
-    // hit points are inside the scene bounds; check the camera (+ lens) here
-    const double cam_mag = std::sqrt(cam->origin[0] * cam->origin[0] + cam->origin[1] * cam->origin[1] +
-                                     cam->origin[2] * cam->origin[2]) + std::fabs(cam->lens_radius) *
-                           (1.0 + std::sqrt(cam->u[0] * cam->u[0] + cam->u[1] * cam->u[1] + cam->u[2] * cam->u[2]) +
-                            std::sqrt(cam->v[0] * cam->v[0] + cam->v[1] * cam->v[1] + cam->v[2] * cam->v[2]));
-    rtk::LaunchOpts o;
-    o.features = c->features | c->extra_features;
-    o.slab32 = c->opt_slab32 && c->pad_extent > 0.0 && cam_mag <= 2.0 * c->pad_extent;
-    o.lds_stack = c->opt_lds && c->S.stack_entries <= kMaxLdsStack;
-    o.count = count;
-    o.f32 = c->opt_precision == RT_PREC_F32;
-    if (sink.moments && o.f32) return fail(RT_ERR_UNSUPPORTED, "adaptive sampling in the f32 mode");
-    if (o.f32 && count && rtk::variant_features(o.features) != rtk::FEAT_SET_SPHERES &&
-        rtk::variant_features(o.features) != rtk::FEAT_SET_FINAL)
-        return fail(RT_ERR_UNSUPPORTED, "count_work in the f32 mode: the spheres and final-scene variants only");
-    if (o.f32) o.slab32 = 1;   // statistical mode: f32 boxes whatever the camera
-    // a scene with no BVH node (the Cornell scenes: one top-level leaf, instances over one
-    // box) tests no slab: the f64-slab instantiation then, which holds no f32 ray terms
-    // (rects + instances variant 125 vs 130 VGPRs: 4 vs 3 waves per SIMD)
-    if (c->n_nodes == 0 && !o.f32) o.slab32 = 0;
-    const long long total = s_end - s_begin;
-    const size_t px_bytes = px * 3 * sizeof(double);
-    // one sample's records in the per-sample buffer: whole 8x8 tiles (trace_kernel.hpp, tiled_record)
-    // (the f32 mode's records are f32: SampleTiles.f32_records; trace_pool writes them so)
-    const rtk::SampleTiles tiles{lay.w, n_rows, (lay.w + 7) / 8, o.f32 ? 1 : 0};
-    const size_t sample_bytes = rtk::tiled_pixels(lay.w, n_rows) * 3 * (o.f32 ? sizeof(float) : sizeof(double));
-    // the TLAS in LDS (read-only, shared by the block) when it fits the per-block budget
-    rtk::SceneDev S = c->S;
-    S.n_lds_nodes = c->opt_lds_nodes ? std::min(c->n_tlas_nodes, kMaxLdsNodes) : 0;
-    // small material and texture tables in LDS too (the variants with rects or media)
-    const bool stage = c->opt_lds_nodes && c->n_materials <= kMaxLdsMaterials && c->n_textures <= kMaxLdsMaterials &&
-                       c->n_materials > 0;
-    S.n_lds_materials = stage ? c->n_materials : 0;
-    S.n_lds_textures = stage ? c->n_textures : 0;
-    // the top levels of the BFS-ordered instance BLAS in LDS too (variants with nested walks),
-    // as many as the LDS left over at the block count the rest of the layout allows
-    S.n_lds_blas = 0;
-    if (c->S.n_blas_bfs > 0 && c->opt_lds_nodes && (rtk::variant_features(o.features) & rtk::FEAT_INST_BLAS) != 0) {
-        const bool oct = o.slab32 && S.n_lds_nodes == c->n_tlas_nodes && S.n_lds_nodes > 0;
-        const uint32_t variant = rtk::variant_features(o.features);
-        const int bt = rtk::block_threads_of(variant, o.f32 != 0);   // workgroup threads (RT_BLOCK_FINAL)
-        const size_t base = (size_t)S.n_lds_nodes * (oct ? 80 : 64) +
-                            (o.lds_stack ? (size_t)c->S.stack_entries * (size_t)bt * 4 : 0) +
-                            (size_t)S.n_lds_materials * 64 + (size_t)S.n_lds_textures * 96;
-        // the CU's 160 KB shared by `blocks` workgroups, each allocation rounded up to the LDS
-        // granule (taken as 1 KB; the occupancy API does not round: a layout it rated at 3
-        // blocks per CU ran 2 and took 174 instead of 133 ms, r03g_ab_c4.log), and no more
-        // workgroups than the variant's registers allow (final scene 4 waves per SIMD, the
-        // all-features variant 3: 16 or 12 waves per CU)
-        const size_t lds_cu = c->lds_per_cu, granule = 1024;
-        const size_t wave_blocks = std::max<size_t>(1, (size_t)(variant == rtk::FEAT_SET_FINAL ? 4 * RT_MIN_WAVES_FINAL : 12) /
-                                                           (size_t)(bt / 64));
-        const size_t blocks = std::max<size_t>(1, std::min(wave_blocks,
-            lds_cu / (((std::max<size_t>(base, 1) + granule - 1) / granule) * granule)));
-        const size_t budget = std::min(lds_cu / blocks, c->lds_per_block) / granule * granule;
-        const size_t spare = budget > base ? budget - base : 0;
-        S.n_lds_blas = (int32_t)std::min<size_t>({(size_t)c->S.n_blas_bfs, spare / 64, (size_t)kMaxLdsBlas});
+// What rt_last_stats shows of a planned range (an empty range: the all-zero plan); the timings,
+// the counters and waves_per_simd are filled when the events resolve.
+static void write_stats(rt_ctx* c, const rtp::Plan& pl, int chunk, int waves_per_simd, bool count)
+{
+    rt_stats& st = c->stats;
+    st.lds_nodes = pl.n_lds_nodes;
+    st.variant_features = (int32_t)pl.variant;
+    st.slab32 = pl.slab32;
+    st.lds_stack = pl.lds_stack;
+    st.schedule = pl.schedule;
+    st.precision = pl.f32 ? RT_PREC_F32 : RT_PREC_F64;
+    st.waves_per_simd = waves_per_simd;
+    st.n_batches = pl.n_batches;
+    st.ring_bytes = (int64_t)pl.ring_bytes;
+    st.trace_buf_bytes = (int64_t)pl.trace_buf_bytes;
+    st.overlapped = pl.overlap ? 1 : 0;
+    st.n_chunks = pl.n_chunks;
+    st.samples = (uint64_t)pl.px * (uint64_t)pl.total;   // (the all-zero plan: px 1, no samples)
+    st.n_items = (uint64_t)pl.px * (uint64_t)pl.n_chunks;
+    st.spp_chunk = chunk;
+    st.node_bytes = (int32_t)sizeof(rt_bvh_node);
+    st.prim_bytes = (int32_t)sizeof(rt_prim);
+    st.material_bytes = (int32_t)sizeof(rt_material);
+    c->pending_stats = true;
+    c->pending_counts = count;
+    if (!st.samples) st.casts = st.node_visits = st.prim_tests = 0;
+}
+
+// Traces samples [s_begin, s_end) of the shard in chunks of `chunk` and reduces them into
+// the sink, as rtp::plan (launch_plan.cpp) lays the range out. Events: ev[0] before the first
+// trace launch, ev[1] after the last one, ev[2] after the last reduction. Chunk and item
+// schedules: chunk partials per launch, reduced in chunk order (or added to the sink's / a
+// running accumulator across buffer batches). Per-sample pool: per-sample radiance in batches;
+// with more than one batch (or an acc sink) the sums run through an accumulator plus the open
+// chunk's sum (carried across batches), which keeps the additions in the one-batch order.
+static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_begin, int s_end, int chunk,
+                     hipStream_t stream, const Sink& sink)
+{
+    const Layout lay = layout_of(p);
+    const long long n_px = (long long)lay.rows * lay.w;
+    if (n_px == 0 || s_end <= s_begin) {
+        // an empty shard (rt_rows_in_shard / rt_tiles_in_shard 0: a rank past the tile count)
+        // or an empty sample range: nothing to trace or write; the events still bracket the
+        // (empty) work so rt_last_stats resolves
+        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventRecord(c->ev[i], stream));
+        write_stats(c, rtp::Plan{}, chunk, 0, false);
+        return RT_OK;
     }
-    // work blocks of one tile: 16-sample chunks, per-sample pool one chunk per block, item pool
-    // two (C2 kernel ms, pool 1/2/4 chunks: 99.8/100.2/103.2; items 1/2/4: 106.8/104.1/105.0;
-    // profiles/r02f_*, r02g_*)
-    K.block_chunks = c->block_chunks > 0 ? c->block_chunks : 2;
-    // Schedule and buffer batches, from the context's trace-output bound (sample_buf_cap). The
-    // bound is sized from the free HBM when the context is created; if the device has less by
-    // now (another context, torch or RCCL allocated since), the allocation below fails and the
-    // bound is halved until it fits: more batches (or the item pool), the same image.
-    // per-sample pool blocks: the chunk's 16 samples per tile while that leaves >= 160 k blocks
-    // (~40 per resident wave), else halved down to 4: a small shard's last blocks would
-    // otherwise leave waves idle (C2 rows of 1 of 8 GPUs: 16 / 8 / 4 samples 14.06 / 13.70 /
-    // 13.57 ms; the whole frame 99.9 / 100.0 / 101.4; scripts/shard_coherence.py, r02p)
-    if (c->block_samples > 0) {
-        K.block_samples = c->block_samples;
-    } else {
-        const long long tiles = (long long)K.tiles_x * K.tiles_y;
-        int bs = chunk;
-        while (bs > 4 && tiles * ((total + bs - 1) / bs) < 160000) bs = (bs + 1) / 2;
-        K.block_samples = bs;
-    }
-    // the pool's in-kernel reduction needs blocks of exactly one chunk (a block's sum is the
-    // chunk's) and batches on chunk boundaries; its ring: kPoolRing blocks for each wave of the
-    // persistent grid (at most 24 per CU: the spheres variant's 6 per SIMD, f64 and f32; the
-    // launch clamps its grid to ring_waves)
-    bool ring_ok = c->opt_ring && K.block_samples == chunk && chunk <= (int)(rtk::kRingSlot / 64) &&
-                   s_end <= (int)rtk::kRingSampleMask;
-    // (the spheres variant runs 6 waves per SIMD: RT_BLOCK_SPHERES, RT_BLOCK_F32_SPHERES)
-    const int ring_waves = c->n_cus * (rtk::variant_features(o.features) == rtk::FEAT_SET_SPHERES ? 24 : 20);
-    const size_t ring_bytes = (size_t)ring_waves * rtk::kRingWaveDoubles * sizeof(double);
-    bool ring = false;
-    bool per_sample = false;
-    long long batch = 0;
-    int n_batches = 0;
-    double* acc = sink.acc;
-    double* open = nullptr;
-    bool own_acc = false;
-    // halved on an out-of-memory retry for this render only: the context's bound stays, so a
-    // later render on it uses the memory freed since
-    size_t buf_cap = c->sample_buf_cap;
-    bool overlap = false;
+
+    const int64_t img_tiles = (int64_t)((p->width + 7) / 8) * ((p->height + 7) / 8);
+    rtk::KParams K;
+    int rc = fill_kparams(c, cam, p, lay, chunk, sink, img_tiles, K);
+    if (rc) return rc;
+
+    rtp::Request rq;
+    rq.lay = lay;
+    rq.s_begin = s_begin;
+    rq.s_end = s_end;
+    rq.chunk = chunk;
+    rq.count_work = p->count_work != 0;
+    rq.acc_sink = sink.acc != nullptr;
+    rq.moments = sink.moments != nullptr;
+    rq.cam_mag = rtp::camera_magnitude(*cam);
+    // the plan, and its buffers: an attempt whose trace output (or ring) does not fit the device
+    // is planned again without the ring, or under half the bound (this render only: the
+    // context's bound stays, so a later render on it uses the memory freed since)
+    rtp::Retry retry{c->sample_buf_cap, true};
+    rtp::Plan pl;
     for (;;) {
-        // AUTO: the per-sample pool when its per-sample radiance is at most 4 times the bound,
-        // else the item pool, whose partials take 1/chunk of those bytes (C5's 1.6 TB: one launch).
-        // Round 2, pool vs items: C2 101.6 vs 106.7 ms per frame, C4 1492 vs 1571 (r02d_*, r02e_*);
-        // round 4: C2 74.75 vs 76.06, C4 1018.5 vs 1074.7; C5 in 25 overlapped pool batches of
-        // 64 GB halves 10,578 ms vs the item pool 10,649 in 64 batches at a 4 GB bound (r04f_*)
-        // AUTO, measured per variant (round 5, profiles/r05x_*, r05w_*, r05y_*): the Cornell box takes
-        // the item pool (C3 800x800x1000: items 204.5 ms, per-sample buffer 209.9, ring 215.0); the
-        // others the per-sample pool — its buffer while that fits the bound in one batch (C1: 2.03 ms,
-        // ring 2.06), else the ring (C2: 74.0 vs 74.7 unbounded; C4 x256: 267.3, items 291.8) — and
-        // the item pool only when neither fits
-        const uint32_t variant = rtk::variant_features(o.features);
-        // (the media variant, Cornell smoke 600x600x200: items 31.72 ms, per-sample buffer 30.28: pool)
-        const bool cornell = variant == rtk::FEAT_SET_RECTINST;
-        const bool fits_one = (size_t)total * sample_bytes <= buf_cap;
-        o.pool = sink.moments                 ? RT_SCHED_POOL
-                 : c->opt_pool != RT_SCHED_AUTO ? c->opt_pool
-                 : cornell && !o.f32 ? RT_SCHED_ITEMS
-                 : (ring_ok || (size_t)total * sample_bytes <= 4 * buf_cap ? RT_SCHED_POOL : RT_SCHED_ITEMS);
-        // POOL with the in-kernel reduction: chunk partials like ITEMS (the ring takes its share of
-        // the bound first, the partials at least one chunk)
-        ring = o.pool == RT_SCHED_POOL && ring_ok && (c->opt_ring == 2 || !fits_one) && !sink.moments;
-        // overlapped batches trace two launches at once, a ring each: a render that does not fit
-        // one batch beside one ring budgets two
-        size_t out_cap = buf_cap;
-        if (ring) {
-            const size_t all = (size_t)((total + chunk - 1) / chunk) * px_bytes;
-            const int rings = c->opt_overlap && all + ring_bytes > buf_cap ? 2 : 1;
-            out_cap = std::max(buf_cap > rings * ring_bytes ? buf_cap - rings * ring_bytes : 0, px_bytes);
-        }
-        // Buffer batches: the trace output is bounded by sample_buf_cap. Per-sample pool: samples x
-        // pixels x 24 B; chunk and item schedules: chunks x pixels x 24 B, batches on chunk
-        // boundaries (relative to s_begin), so the partials add in one-launch order. A render that
-        // does not fit in one batch takes two buffers of half the bound: batch k traces into half
-        // k & 1 on stream tstream[k & 1] while the caller's stream reduces batch k - 1, so the
-        // next trace fills the CUs its predecessor's last waves leave (no tail per batch).
-        per_sample = o.pool == RT_SCHED_POOL && !ring;
-        const size_t unit = per_sample ? sample_bytes : px_bytes;
-        long long fit = (long long)std::max<size_t>(1, out_cap / unit);
-        batch = std::min<long long>(total, per_sample ? fit : fit * chunk);
-        // (only with 256-thread workgroups: a batch's launch of the large-workgroup variants —
-        // the spheres variant's 768 threads, the final scene's 1024 — takes a CU only when a whole
-        // workgroup of its predecessor has left, and the two persistent grids then contend instead:
-        // C5 4096x4096x4096 overlapped 11,471 ms per frame, in order 10,474, profiles/r06zz_c5_*)
-        const bool big_wg = rtk::block_threads_of(variant, o.f32 != 0,
-                                                  o.slab32 && o.lds_stack && S.n_lds_nodes > 0 &&
-                                                      S.n_lds_nodes == c->n_tlas_nodes && S.stack16_ok) > 256;
-        overlap = c->opt_overlap && !big_wg && batch < total && o.pool != RT_SCHED_CHUNKS;
-        if (overlap) {
-            fit = (long long)std::max<size_t>(1, out_cap / 2 / unit);
-            batch = std::min<long long>(total, per_sample ? fit : fit * chunk);
-        }
-        n_batches = (int)((total + batch - 1) / batch);
-        acc = sink.acc;
-        open = nullptr;
-        own_acc = false;
+        pl = rtp::plan(c->scene, c->dev, c->opt, rq, retry);
+        if (pl.err) return fail(pl.err, pl.err_msg);
+        rc = grow(c, stream, c->acc_tmp, c->acc_tmp_cap, pl.acc_bytes);
+        if (rc) return rc;
         bool oom = false;
-        int rc = RT_OK;
-        // (an adaptive pass keeps its sums and the open chunk in the call's frame-layout accumulators)
-        if (per_sample && !sink.moments && (n_batches > 1 || acc)) {  // acc_tmp = [open chunk sums | running total (no acc sink)]
-            rc = grow(c, stream, c->acc_tmp, c->acc_tmp_cap, 2 * px_bytes);
-            if (rc) return rc;
-            open = c->acc_tmp;
-            if (!acc) {
-                acc = c->acc_tmp + px * 3;
-                own_acc = true;
-            }
-        } else if (!per_sample && n_batches > 1 && !acc) {  // running total of the chunk partials
-            rc = grow(c, stream, c->acc_tmp, c->acc_tmp_cap, px_bytes);
-            if (rc) return rc;
-            acc = c->acc_tmp;
-            own_acc = true;
-        }
-        const int max_chunks = (int)((batch + chunk - 1) / chunk);
-        const size_t half = per_sample ? (size_t)batch * sample_bytes : (size_t)max_chunks * px_bytes;
-        const size_t need = overlap ? 2 * half : half;
-        rc = grow(c, stream, c->partial, c->partial_cap, need, &oom);
-        if (rc == RT_OK && ring) {
-            rc = grow(c, stream, c->ring, c->ring_cap, (overlap ? 2 : 1) * ring_bytes, &oom);
+        rc = grow(c, stream, c->partial, c->partial_cap, pl.partial_bytes, &oom);
+        if (rc == RT_OK && pl.ring) {
+            rc = grow(c, stream, c->ring, c->ring_cap, pl.ring_bytes, &oom);
             if (rc != RT_OK && oom) {   // no room for the ring: the per-sample buffer, as before
-                ring_ok = false;
+                retry.ring_allowed = false;
                 continue;
             }
         }
         if (rc == RT_OK) break;
         if (!oom) return rc;
-        if (buf_cap <= ((size_t)1 << 20) || need <= (per_sample ? sample_bytes : px_bytes))
-            return hip_fail(hipErrorOutOfMemory, "trace output buffer (smallest batch)");
-        buf_cap = std::max<size_t>(buf_cap / 2, (size_t)1 << 20);
+        if (!rtp::shrink(pl, retry)) return hip_fail(hipErrorOutOfMemory, "trace output buffer (smallest batch)");
     }
-    if (own_acc) HIP_TRY(hipMemsetAsync(acc, 0, px_bytes, stream));
-    K.ring_waves = ring ? ring_waves : 0;
-    if (count) {
+    // acc_tmp = [open chunk sums | running total (no acc sink)], or the running total alone
+    double* const open = pl.open_chunk ? c->acc_tmp : nullptr;
+    double* const acc = !pl.own_total ? sink.acc : pl.open_chunk ? c->acc_tmp + pl.px * 3 : c->acc_tmp;
+    rtk::SceneDev S = c->S;
+    S.n_lds_nodes = pl.n_lds_nodes;
+    S.n_lds_materials = pl.n_lds_materials;
+    S.n_lds_textures = pl.n_lds_textures;
+    S.n_lds_blas = pl.n_lds_blas;
+    K.block_chunks = pl.block_chunks;
+    K.block_samples = pl.block_samples;
+    K.ring_waves = pl.ring_waves;
+    int waves_per_simd = 0;
+    rtk::LaunchOpts o;
+    o.features = pl.features;
+    o.slab32 = pl.slab32;
+    o.lds_stack = pl.lds_stack;
+    o.count = rq.count_work;
+    o.pool = pl.schedule;
+    o.f32 = pl.f32;
+    o.waves_per_simd = &waves_per_simd;
+    const rtk::SampleTiles tiles{lay.w, lay.rows, (lay.w + 7) / 8, pl.f32};
+
+    if (pl.own_total) HIP_TRY(hipMemsetAsync(acc, 0, pl.px_bytes, stream));
+    if (rq.count_work) {
         HIP_TRY(hipMemsetAsync(c->counters, 0, kCounters * sizeof(unsigned long long), stream));
         if (img_tiles > c->tile_cost_cap) {   // (a render's first use: no work on the context's streams reads it)
             HIP_TRY(hipStreamSynchronize(stream));
@@ -1000,91 +810,63 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
         HIP_TRY(hipMemsetAsync(c->tile_cost, 0, (size_t)img_tiles * sizeof(unsigned long long), stream));
         K.tile_cost = c->tile_cost;
         // (the pool kernels count them; the chunk schedule does not)
-        c->tile_cost_n = o.pool == RT_SCHED_POOL || o.pool == RT_SCHED_ITEMS ? img_tiles : 0;
+        c->tile_cost_n = pl.schedule == RT_SCHED_POOL || pl.schedule == RT_SCHED_ITEMS ? img_tiles : 0;
     }
-    int waves_per_simd = 0;
-    o.waves_per_simd = &waves_per_simd;
     HIP_TRY(hipEventRecord(c->ev[0], stream));
     // overlapped batches: both trace streams start after everything enqueued on `stream` so far
-    if (overlap) {
+    if (pl.overlap) {
         HIP_TRY(hipEventRecord(c->ev_in, stream));
         for (int i = 0; i < 2; ++i) HIP_TRY(hipStreamWaitEvent(c->tstream[i], c->ev_in, 0));
     }
-    const size_t half_elems = overlap ? (per_sample ? (size_t)batch * sample_bytes
-                                                    : (size_t)((batch + chunk - 1) / chunk) * px_bytes) / sizeof(double)
-                                      : 0;
-    for (int bi = 0; bi < n_batches; ++bi) {
-        const int b0 = s_begin + (int)(bi * batch);
-        const int b1 = (int)std::min<long long>(s_end, b0 + batch);
+    for (int bi = 0; bi < pl.n_batches; ++bi) {
+        const int b0 = s_begin + (int)(bi * pl.batch);
+        const int b1 = (int)std::min<long long>(s_end, b0 + pl.batch);
         K.sample_begin = b0;
         K.spp = b1;
         K.n_chunks = (b1 - b0 + chunk - 1) / chunk;
         {
-            const unsigned g = o.pool == RT_SCHED_ITEMS ? (unsigned)K.block_chunks : (unsigned)K.block_samples;   // (POOL: samples)
-            const unsigned n = o.pool == RT_SCHED_ITEMS ? (unsigned)K.n_chunks : (unsigned)(K.spp - K.sample_begin);
+            const bool items = pl.schedule == RT_SCHED_ITEMS;
+            const unsigned g = items ? (unsigned)K.block_chunks : (unsigned)K.block_samples;   // (POOL: samples)
+            const unsigned n = items ? (unsigned)K.n_chunks : (unsigned)(K.spp - K.sample_begin);
             const unsigned n_groups = (n + g - 1) / std::max(g, 1u);
             K.n_work_blocks = (unsigned)K.tiles_x * (unsigned)K.tiles_y * n_groups;
             K.deal_div = K.tile_major ? n_groups : (unsigned)K.tiles_x * (unsigned)K.tiles_y;
         }
         // batch bi's buffer half, trace stream and work counter (one of each per overlapped batch)
-        const int h = overlap ? (bi & 1) : 0;
-        double* buf = c->partial + (size_t)h * half_elems;
-        hipStream_t ts = overlap ? c->tstream[h] : stream;
-        K.ring = ring ? c->ring + (size_t)h * (ring_bytes / sizeof(double)) : nullptr;   // one ring per trace stream
-        if (overlap && bi >= 2) HIP_TRY(hipStreamWaitEvent(ts, c->ev_rd[h], 0));   // batch bi - 2 reduced: half free
+        const int h = pl.overlap ? (bi & 1) : 0;
+        double* buf = c->partial + (size_t)h * (pl.half_bytes / sizeof(double));
+        hipStream_t ts = pl.overlap ? c->tstream[h] : stream;
+        K.ring = pl.ring ? c->ring + (size_t)h * (pl.ring_one_bytes / sizeof(double)) : nullptr;   // one ring per trace stream
+        if (pl.overlap && bi >= 2) HIP_TRY(hipStreamWaitEvent(ts, c->ev_rd[h], 0));   // batch bi - 2 reduced: half free
         rtk::KParams* dK = c->params + c->param_slot;
         c->param_slot = (c->param_slot + 1) % kParamSlots;
         HIP_TRY(hipMemcpyAsync(dK, &K, sizeof K, hipMemcpyHostToDevice, ts));
         HIP_TRY(rtk::launch_trace(S, K, dK, buf, c->counters, c->work + h, o, ts));
-        if (bi == n_batches - 1) HIP_TRY(hipEventRecord(c->ev[1], ts));
-        if (overlap) {   // reduce in batch order on `stream`, after this batch's trace
+        if (bi == pl.n_batches - 1) HIP_TRY(hipEventRecord(c->ev[1], ts));
+        if (pl.overlap) {   // reduce in batch order on `stream`, after this batch's trace
             HIP_TRY(hipEventRecord(c->ev_tr[h], ts));
             HIP_TRY(hipStreamWaitEvent(stream, c->ev_tr[h], 0));
         }
         if (sink.moments) {
             HIP_TRY(rtk::launch_adaptive_moments(buf, *sink.moments, K.tiles_x, b1 - b0, chunk,
-                                                 (int)(((long long)b0 - s_begin) % chunk), bi == n_batches - 1,
+                                                 (int)(((long long)b0 - s_begin) % chunk), bi == pl.n_batches - 1,
                                                  sink.n_done, stream));
-        } else if (!per_sample) {
+        } else if (!pl.per_sample) {
             if (acc) HIP_TRY(rtk::launch_accumulate(buf, acc, n_px, K.n_chunks, stream));
             else HIP_TRY(rtk::launch_reduce(buf, sink.out, sink.f64, n_px, K.n_chunks, sink.scale, stream));
         } else if (!open) {
             HIP_TRY(rtk::launch_reduce_samples(buf, sink.out, sink.f64, tiles, b1 - b0, chunk, sink.scale, stream));
         } else {
             HIP_TRY(rtk::launch_reduce_samples_carry(buf, acc, open, tiles, b1 - b0, chunk,
-                                                     (int)(((long long)b0 - s_begin) % chunk), bi == n_batches - 1,
+                                                     (int)(((long long)b0 - s_begin) % chunk), bi == pl.n_batches - 1,
                                                      stream));
         }
-        if (overlap) HIP_TRY(hipEventRecord(c->ev_rd[h], stream));
+        if (pl.overlap) HIP_TRY(hipEventRecord(c->ev_rd[h], stream));
     }
-    if (own_acc)  // resolve the running sums: 0.0 + sum, times scale, as one batch does
+    if (pl.own_total)  // resolve the running sums: 0.0 + sum, times scale, as one batch does
         HIP_TRY(rtk::launch_reduce(acc, sink.out, sink.f64, n_px, 1, sink.scale, stream));
     HIP_TRY(hipEventRecord(c->ev[2], stream));
-
-    c->stats.lds_nodes = S.n_lds_nodes;
-    c->stats.variant_features = (int32_t)rtk::variant_features(o.features);
-    c->stats.slab32 = o.slab32;
-    c->stats.lds_stack = o.lds_stack;
-    c->stats.schedule = o.pool;
-    c->stats.precision = o.f32 ? RT_PREC_F32 : RT_PREC_F64;
-    c->stats.waves_per_simd = waves_per_simd;
-    c->stats.n_batches = n_batches;
-    c->stats.ring_bytes = ring ? (int64_t)((overlap ? 2 : 1) * ring_bytes) : 0;
-    c->stats.trace_buf_bytes = (int64_t)(overlap ? 2 * half_elems * sizeof(double)
-                                                 : (per_sample ? (size_t)batch * sample_bytes
-                                                               : (size_t)((batch + chunk - 1) / chunk) * px_bytes)) +
-                               c->stats.ring_bytes;
-    c->stats.overlapped = overlap ? 1 : 0;
-    c->stats.samples = (uint64_t)n_px * (uint64_t)total;
-    c->stats.n_chunks = (int32_t)((total + chunk - 1) / chunk);
-    c->stats.n_items = (uint64_t)n_px * (uint64_t)c->stats.n_chunks;
-    c->stats.spp_chunk = chunk;
-    c->stats.node_bytes = (int32_t)sizeof(rt_bvh_node);
-    c->stats.prim_bytes = (int32_t)sizeof(rt_prim);
-    c->stats.material_bytes = (int32_t)sizeof(rt_material);
-    c->pending_stats = true;
-    c->pending_counts = count;
-    if (!c->stats.samples) c->stats.casts = c->stats.node_visits = c->stats.prim_tests = 0;
+    write_stats(c, pl, chunk, waves_per_simd, rq.count_work);
     return RT_OK;
 }
 
@@ -1401,7 +1183,7 @@ int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
         return fail(RT_ERR_INVALID, "bad render params (adaptive sampling needs spp >= 2)");
     if (ap->min_spp < 2 || ap->step_spp < 1 || std::isnan(ap->threshold))
         return fail(RT_ERR_INVALID, "bad adaptive params (min_spp >= 2, step_spp >= 1, threshold not NaN)");
-    if (c->opt_precision == RT_PREC_F32) return fail(RT_ERR_UNSUPPORTED, "adaptive sampling in the f32 mode");
+    if (c->opt.precision == RT_PREC_F32) return fail(RT_ERR_UNSUPPORTED, "adaptive sampling in the f32 mode");
     const int W = p->width, H = p->height, tiles_x = (W + 7) / 8;
     const long long tiles_ll = (long long)tiles_x * ((H + 7) / 8);
     if (tiles_ll > 0x3fffffffLL) return fail(RT_ERR_INVALID, "too many tiles");
@@ -1747,16 +1529,16 @@ int rt_ctx_set_variant(rt_ctx* c, int slab32, int lds_stack, int lds_nodes)
 {
     if (!c || slab32 < 0 || slab32 > 1 || lds_stack < 0 || lds_stack > 1 || lds_nodes < 0 || lds_nodes > 1)
         return fail(RT_ERR_INVALID, "bad variant");
-    c->opt_slab32 = slab32;
-    c->opt_lds = lds_stack;
-    c->opt_lds_nodes = lds_nodes;
+    c->opt.slab32 = slab32;
+    c->opt.lds_stack = lds_stack;
+    c->opt.lds_nodes = lds_nodes;
     return RT_OK;
 }
 
 int rt_ctx_set_precision(rt_ctx* c, int precision)
 {
     if (!c || (precision != RT_PREC_F64 && precision != RT_PREC_F32)) return fail(RT_ERR_INVALID, "bad precision");
-    c->opt_precision = precision;
+    c->opt.precision = precision;
     return RT_OK;
 }
 
@@ -1768,23 +1550,23 @@ int rt_ctx_set_option(rt_ctx* c, int key, int64_t v)
         if (v < 0) return fail(RT_ERR_INVALID, "negative buffer bound");
         c->sample_buf_cap = v == 0 ? default_buf_cap() : std::max<size_t>((size_t)v, (size_t)1 << 20);
         return RT_OK;
-    case RT_OPT_BATCH_OVERLAP: c->opt_overlap = v != 0; return RT_OK;
+    case RT_OPT_BATCH_OVERLAP: c->opt.overlap = v != 0; return RT_OK;
     case RT_OPT_BLOCK_SAMPLES:
         if (v < 0 || v > 1024) return fail(RT_ERR_INVALID, "block samples out of range (0..1024)");
-        c->block_samples = (int)v;
+        c->opt.block_samples = (int)v;
         return RT_OK;
     case RT_OPT_BLOCK_CHUNKS:
         if (v < 0 || v > 64) return fail(RT_ERR_INVALID, "block chunks out of range (0..64)");
-        c->block_chunks = (int)v;
+        c->opt.block_chunks = (int)v;
         return RT_OK;
     case RT_OPT_EXTRA_FEATURES:
         if (v < 0 || (v & ~(int64_t)rtk::FEAT_ALL)) return fail(RT_ERR_INVALID, "unknown feature bits");
-        c->extra_features = (uint32_t)v;
+        c->opt.extra_features = (uint32_t)v;
         return RT_OK;
     case RT_OPT_HOIST: c->opt_hoist = v != 0; return RT_OK;
     case RT_OPT_POOL_RING:
         if (v < 0 || v > 2) return fail(RT_ERR_INVALID, "pool ring mode out of range (0 never, 1 when needed, 2 always)");
-        c->opt_ring = (int)v;
+        c->opt.ring = (int)v;
         return RT_OK;
     case RT_OPT_COMM_DIRECT: c->opt_comm_direct = v != 0; return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
@@ -1796,12 +1578,12 @@ int rt_ctx_get_option(rt_ctx* c, int key, int64_t* v)
     if (!c || !v) return fail(RT_ERR_INVALID, "null argument");
     switch (key) {
     case RT_OPT_TRACE_BUF_BYTES: *v = (int64_t)c->sample_buf_cap; return RT_OK;
-    case RT_OPT_BATCH_OVERLAP: *v = c->opt_overlap; return RT_OK;
-    case RT_OPT_BLOCK_SAMPLES: *v = c->block_samples; return RT_OK;
-    case RT_OPT_BLOCK_CHUNKS: *v = c->block_chunks; return RT_OK;
-    case RT_OPT_EXTRA_FEATURES: *v = c->extra_features; return RT_OK;
+    case RT_OPT_BATCH_OVERLAP: *v = c->opt.overlap; return RT_OK;
+    case RT_OPT_BLOCK_SAMPLES: *v = c->opt.block_samples; return RT_OK;
+    case RT_OPT_BLOCK_CHUNKS: *v = c->opt.block_chunks; return RT_OK;
+    case RT_OPT_EXTRA_FEATURES: *v = c->opt.extra_features; return RT_OK;
     case RT_OPT_HOIST: *v = c->opt_hoist; return RT_OK;
-    case RT_OPT_POOL_RING: *v = c->opt_ring; return RT_OK;
+    case RT_OPT_POOL_RING: *v = c->opt.ring; return RT_OK;
     case RT_OPT_COMM_DIRECT: *v = c->opt_comm_direct; return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
@@ -1812,7 +1594,7 @@ int rt_ctx_set_schedule(rt_ctx* c, int schedule)
     if (c && schedule == 4)   // the wavefront schedule of ABI v4 (rejected, scripts/experiments/r05_wavefront.patch)
         return fail(RT_ERR_UNSUPPORTED, "schedule 4 (wavefront) was removed: 2.3x slower than the pool on C4 (DESIGN.md 5.7)");
     if (!c || schedule < RT_SCHED_CHUNKS || schedule > RT_SCHED_AUTO) return fail(RT_ERR_INVALID, "bad schedule");
-    c->opt_pool = schedule;
+    c->opt.schedule = schedule;
     return RT_OK;
 }
 
@@ -1848,7 +1630,7 @@ const uint32_t* ctx_tile_order(const rt_ctx* c, int64_t* n)
     *n = c->tile_order_n;
     return c->tile_order;
 }
-int ctx_schedule(const rt_ctx* c) { return c->opt_pool; }
-int ctx_precision(const rt_ctx* c) { return c->opt_precision; }
+int ctx_schedule(const rt_ctx* c) { return c->opt.schedule; }
+int ctx_precision(const rt_ctx* c) { return c->opt.precision; }
 bool ctx_comm_direct(const rt_ctx* c) { return c->opt_comm_direct != 0; }
 }  // namespace rtx

@@ -1,7 +1,8 @@
 // ctx_internal.hpp — what comm.cpp (the multi-GPU entry points) reads of a context that the
 // C ABI does not show: its device, its stream, its tile order and tile costs on the device,
 // and the last-error slot of the calling thread. Implemented in abi.cpp; not exported in
-// include/rt/rt_abi.h.
+// include/rt/rt_abi.h. (What a render launches under these settings — the schedule AUTO resolves
+// to, whether buffer batches overlap — is decided in launch_plan.cpp.)
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -2649,6 +2649,8 @@ static void launch_f(const Launch& L, int slab32, int lds, hipStream_t stream)
     bool nall = S.n_lds_nodes > 0 && S.n_lds_nodes == S.n_tlas_nodes;
     // the whole-TLAS spheres instantiation keeps 16-bit stack entries (Stack16Cfg): a scene
     // whose node addresses or leaf codes do not fit takes the partial-TLAS instantiation
+    // (the host's plan sizes overlap and LDS from the workgroup this ends in: launch_shapes.hpp
+    // stack16_launch states the same test in one expression; the two must agree)
     constexpr bool S16F = F == FEAT_SET_SPHERES;   // Stack16Cfg's feature set
     if (RT_STACK16 && S16F && slab32 && lds && !S.stack16_ok) nall = false;
     // stack16_ok (scene_lower.cpp) assumes the node records start at LDS address 0, i.e. that rt_lds is

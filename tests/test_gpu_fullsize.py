@@ -284,7 +284,7 @@ def test_overlapped_buffer_batches_at_c2_size(rt, renderer, sched):
     (per-sample pool: 5 samples per half, 10 batches; item pool: chunks of 3, 5 chunks per half,
     4 batches) equals the one-batch render bit for bit, and so does the same bound without
     overlap (RT_OPT_BATCH_OVERLAP 0: 11 samples or chunks per batch, 5 and 2 batches). Batches
-    overlap only for kernels of 256-thread workgroups (abi.cpp): the overlapped runs take the
+    overlap only for kernels of 256-thread workgroups (launch_plan.cpp): the overlapped runs take the
     random scene's partial-TLAS instantiation (lds_nodes 0: 256 threads); the default one (768-
     thread workgroups, 6 waves per SIMD) runs its batches in order, as with the option at 0."""
     W, H, spp = 1200, 800, 48

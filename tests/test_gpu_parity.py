@@ -429,7 +429,7 @@ def test_schedules_render_identically(rt, scene_id, W, H, spp):
     batched = small.render(cam, q)
     # 256-thread-workgroup variants (Cornell scenes): overlapped, 5 x 7 + 5 samples in the bound's
     # halves, chunks of 3 straddle batches; the random and final scenes' variants (768 / 1024
-    # threads) run their batches in order, 14 + 14 + 12 samples (abi.cpp, RT_OPT_BATCH_OVERLAP)
+    # threads) run their batches in order, 14 + 14 + 12 samples (launch_plan.cpp, RT_OPT_BATCH_OVERLAP)
     assert small.stats().n_batches == (6 if scene_id in (5, 6) else 3)
     assert np.array_equal(batched, one)
     serial.set_schedule(rt.RT_SCHED_POOL)
