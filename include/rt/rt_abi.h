@@ -281,8 +281,27 @@ int rt_last_tile_costs(rt_ctx* ctx, uint64_t* out, int64_t n);
  * shards of nearly equal cost, each finishing its expensive tiles first and ending on its
  * cheapest ones (a shard's launch otherwise ends on the last sample group of its most
  * expensive tiles). Only which pixels a shard renders, and when, changes, not their bits.
- * n = 0: raster order again (the default). Waits for the device. */
+ * n = 0: raster order again (the default). Waits for the device.
+ *
+ * Whole frames need no such call (RT_OPT_AUTO_DEAL_ORDER, default on): a render that is not a
+ * tile or row shard, not count_work, not an rt_render_adaptive pass, on a pool schedule (POOL with
+ * its buffer or its ring, ITEMS; every buffer batch; f64 and f32) is dealt tile-major in a cost
+ * order the context measures for itself. The first such render of a (scene upload, camera, width,
+ * height) runs tile-major in raster order while its trace kernel adds, per work block, the wave's
+ * cycles until its next block fetch to the block's tile; the second reads those costs back once
+ * (8 bytes per tile, one stream synchronization inside that call), sorts them as
+ * rt_cost_tile_order does and uploads the order; every later one, at any spp, seed, depth or
+ * sample range (rt_accum_add, rt_render_progressive), reuses it with no host work. Only the order
+ * blocks are handed out in changes: records, the reduction and the frame stay raster, so no bit
+ * changes. A new upload or another key drops the order. The spheres kernel variants carry it
+ * (scenes of spheres and moving spheres: the random scenes); scenes on the other variants keep
+ * raster order. This context order (rt_ctx_set_tile_order) and the tile shards
+ * it serves are not affected. */
 int rt_ctx_set_tile_order(rt_ctx* ctx, const uint32_t* order, int64_t n);
+/* The order the last render was dealt in under RT_OPT_AUTO_DEAL_ORDER: copies min(n, tiles)
+ * entries (position -> raster tile) and returns the tile count, or 0 when it was dealt in raster
+ * order (a key's first render, an ineligible render, option 0 or 2). */
+int rt_last_deal_order(rt_ctx* ctx, uint32_t* out, int64_t n);
 
 /* ---- multi-GPU render: tile shards, one RCCL gather, on-device reassembly (ABI v5) ------------
  * The reference splits one frame over 10 threads (main.rs:497-551: every thread all pixels,
@@ -563,7 +582,10 @@ int rt_ctx_set_variant(rt_ctx* ctx, int slab32, int lds_stack, int lds_nodes);
  *   RT_OPT_COMM_DIRECT      1 (default): rt_render_gather on a communicator of one rank, with the
  *                           context in raster tile order, is rt_render straight into the frame (a
  *                           world of one has nothing to gather); 0: the tile shard, the RCCL gather
- *                           and the reorder kernel as at any other world size (tests) */
+ *                           and the reorder kernel as at any other world size (tests)
+ *   RT_OPT_AUTO_DEAL_ORDER  1 (default): whole-frame pool renders are dealt in the cost order the
+ *                           render itself measured (rt_last_deal_order); 0: raster order, nothing
+ *                           measured; 2: every render measures, none is reordered (A/B runs) */
 enum {
     RT_OPT_TRACE_BUF_BYTES = 1,
     RT_OPT_BATCH_OVERLAP = 2,
@@ -573,7 +595,8 @@ enum {
     RT_OPT_HOIST = 6,
     /* 7, 8: ABI v4's wavefront-schedule options, removed with it (RT_ERR_INVALID) */
     RT_OPT_POOL_RING = 9,
-    RT_OPT_COMM_DIRECT = 10
+    RT_OPT_COMM_DIRECT = 10,
+    RT_OPT_AUTO_DEAL_ORDER = 11
 };
 int rt_ctx_set_option(rt_ctx* ctx, int key, int64_t value);
 int rt_ctx_get_option(rt_ctx* ctx, int key, int64_t* value);

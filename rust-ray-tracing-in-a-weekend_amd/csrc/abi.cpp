@@ -16,6 +16,7 @@
 #include "rt/rt_abi.h"
 #include "adaptive_criterion.hpp"
 #include "ctx_internal.hpp"
+#include "deal_cache.hpp"
 #include "denoise.hpp"
 #include "launch_plan.hpp"
 #include "scene_lower.hpp"
@@ -102,13 +103,21 @@ struct rt_ctx {
     int64_t tile_cost_n = 0;            //   tiles of the last count_work render (rt_last_tile_costs)
     int opt_hoist = 1;                  // RT_OPT_HOIST: test a huge root-child leaf before the walk (pre_leaf)
     size_t sample_buf_cap = (size_t)32 << 30;  // RT_OPT_TRACE_BUF_BYTES: bound of the trace-output buffer
-    unsigned* work = nullptr;           // pool / item schedules: work-block counters (one per overlapped batch)
+    unsigned* work = nullptr;           // pool / item schedules: work-block counters (one per overlapped batch),
+    size_t work_stride = rtk::kDealTable;   //   work_stride words apart: each one's deal table and tile costs follow it
     // Overlapped buffer batches (RT_OPT_BATCH_OVERLAP): batch k traces on tstream[k & 1] into half k & 1
     // of the trace-output buffer while the caller's stream reduces batch k - 1
     hipStream_t tstream[2] = {nullptr, nullptr};
     hipEvent_t ev_in = nullptr, ev_tr[2] = {nullptr, nullptr}, ev_rd[2] = {nullptr, nullptr};
     double* acc_tmp = nullptr;          // running sums when a render takes several buffer batches
     size_t acc_tmp_cap = 0;
+    // RT_OPT_AUTO_DEAL_ORDER (deal_cache.hpp): whole-frame pool renders dealt in the cost order the
+    // product kernel measured on the first render of a (scene upload, camera, frame)
+    int opt_deal = rtd::kAuto;
+    uint64_t upload_gen = 0;            // scene uploads so far (the cache's key)
+    rtd::DealCache deal;
+    int64_t deal_cap = 0;               // tiles the deal tables behind the work counters hold (trace_kernel.hpp, kDealTable)
+    int64_t last_deal_n = 0;            // tiles of the order the last render was dealt in (0: raster; rt_last_deal_order)
 };
 
 // The trace-output buffer's default bound: 64 GiB, or half the device's free memory if that is
@@ -176,7 +185,7 @@ int rt_ctx_create(int device, rt_ctx** out)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMalloc((void**)&c->counters, kCounters * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc((void**)&c->params, kParamSlots * sizeof(rtk::KParams));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->work, 2 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->work, 2 * rtk::kDealTable * sizeof(unsigned));
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipStreamCreateWithFlags(&c->tstream[i], hipStreamNonBlocking);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->ev_tr[i], hipEventDisableTiming);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->ev_rd[i], hipEventDisableTiming);
@@ -517,6 +526,9 @@ int rt_ctx_upload_soa(rt_ctx* c, const rt_scene_soa* s)
     std::string err;
     const int rc = rtl::lower(*s, c->opt_hoist != 0, L, err);
     if (rc) return fail(rc, err);
+    c->upload_gen++;   // the scene's tables are replaced below: a measured deal order is another scene's
+    c->deal.drop();
+    c->last_deal_n = 0;
 
     struct Table {
         const void* src;
@@ -688,6 +700,74 @@ static int fill_kparams(rt_ctx* c, const rt_camera* cam, const rt_render_params*
     return RT_OK;
 }
 
+// The whole-frame deal order (deal_cache.hpp): what the cache decides for this render, carried out.
+// The table and the tile costs follow each of the two work counters in memory (trace_kernel.hpp,
+// kDealTable). A measuring render uploads the identity table, zeroes the costs and launches with
+// tile_major = kDealMeasure; the next one of the key reads the costs back (the one synchronization,
+// inside this call), builds the order and uploads it; later ones only set tile_major =
+// kDealOrdered. `stream` already waits for the context's earlier work.
+static int deal_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rtp::Plan& pl, bool adaptive_pass,
+                      int64_t img_tiles, hipStream_t stream, rtk::KParams& K)
+{
+    c->last_deal_n = 0;
+    const bool ok = rtk::deal_variant(pl.variant) && rtd::eligible(*p, pl.schedule, adaptive_pass);
+    const rtd::Decision d = c->deal.next(c->opt_deal, ok, rtd::key_of(c->upload_gen, *cam, *p), img_tiles);
+    const size_t n = (size_t)img_tiles;
+    if (d.measure) {
+        if (img_tiles > c->deal_cap) {   // (a key's first render: no work on the context's streams reads them)
+            HIP_TRY(hipStreamSynchronize(stream));
+            const size_t stride = rtk::kDealTable + 2 * n;
+            unsigned* w = nullptr;
+            const hipError_t e = hipMalloc((void**)&w, 2 * stride * sizeof(unsigned));
+            if (e != hipSuccess) {
+                c->deal.drop();
+                return hip_fail(e, "deal order table");
+            }
+            (void)hipFree(c->work);
+            c->work = w;
+            c->work_stride = stride;
+            c->deal_cap = img_tiles;
+        }
+        std::vector<uint32_t> raster(n);
+        for (size_t i = 0; i < n; ++i) raster[i] = (uint32_t)i;
+        for (int h = 0; h < 2; ++h) {
+            unsigned* t = c->work + h * c->work_stride + rtk::kDealTable;
+            HIP_TRY(hipMemcpyAsync(t, raster.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemsetAsync(t + n, 0, n * sizeof(unsigned), stream));
+        }
+        HIP_TRY(hipStreamSynchronize(stream));   // (raster is pageable and local)
+        K.tile_major = rtk::kDealMeasure;
+    }
+    if (d.build) {
+        std::vector<uint32_t> part(2 * n);
+        hipError_t e = hipSuccess;
+        for (int h = 0; h < 2 && e == hipSuccess; ++h)
+            e = hipMemcpyAsync(part.data() + h * n, c->work + h * c->work_stride + rtk::kDealTable + n, n * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) {
+            c->deal.fail_build();
+            return hip_fail(e, "deal order: tile costs");
+        }
+        std::vector<uint64_t> costs(n);   // (overlapped batches count on both counters' tables)
+        for (size_t i = 0; i < n; ++i) costs[i] = (uint64_t)part[i] + part[n + i];
+        const std::vector<uint32_t>& order = c->deal.finish_build(costs.data());
+        for (int h = 0; h < 2 && e == hipSuccess; ++h)
+            e = hipMemcpyAsync(c->work + h * c->work_stride + rtk::kDealTable, order.data(), n * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (the pageable copy's source is the cache's, kept; the sync is cheap here)
+        if (e != hipSuccess) {
+            c->deal.fail_build();
+            return hip_fail(e, "deal order: upload");
+        }
+    }
+    if (d.ordered) {
+        K.tile_major = rtk::kDealOrdered;
+        c->last_deal_n = img_tiles;
+    }
+    return RT_OK;
+}
+
 // What rt_last_stats shows of a planned range (an empty range: the all-zero plan); the timings,
 // the counters and waves_per_simd are filled when the events resolve.
 static void write_stats(rt_ctx* c, const rtp::Plan& pl, int chunk, int waves_per_simd, bool count)
@@ -734,6 +814,7 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
         // (empty) work so rt_last_stats resolves
         for (int i = 0; i < 3; ++i) HIP_TRY(hipEventRecord(c->ev[i], stream));
         write_stats(c, rtp::Plan{}, chunk, 0, false);
+        c->last_deal_n = 0;
         return RT_OK;
     }
 
@@ -795,6 +876,8 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
     o.f32 = pl.f32;
     o.waves_per_simd = &waves_per_simd;
     const rtk::SampleTiles tiles{lay.w, lay.rows, (lay.w + 7) / 8, pl.f32};
+    rc = deal_setup(c, cam, p, pl, sink.moments != nullptr, img_tiles, stream, K);
+    if (rc) return rc;
 
     if (pl.own_total) HIP_TRY(hipMemsetAsync(acc, 0, pl.px_bytes, stream));
     if (rq.count_work) {
@@ -841,7 +924,7 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
         rtk::KParams* dK = c->params + c->param_slot;
         c->param_slot = (c->param_slot + 1) % kParamSlots;
         HIP_TRY(hipMemcpyAsync(dK, &K, sizeof K, hipMemcpyHostToDevice, ts));
-        HIP_TRY(rtk::launch_trace(S, K, dK, buf, c->counters, c->work + h, o, ts));
+        HIP_TRY(rtk::launch_trace(S, K, dK, buf, c->counters, c->work + h * c->work_stride, o, ts));
         if (bi == pl.n_batches - 1) HIP_TRY(hipEventRecord(c->ev[1], ts));
         if (pl.overlap) {   // reduce in batch order on `stream`, after this batch's trace
             HIP_TRY(hipEventRecord(c->ev_tr[h], ts));
@@ -1454,6 +1537,16 @@ int rt_ctx_set_tile_order(rt_ctx* c, const uint32_t* order, int64_t n)
     return RT_OK;
 }
 
+int rt_last_deal_order(rt_ctx* c, uint32_t* out, int64_t n)
+{
+    if (!c || (!out && n > 0) || n < 0) return fail(RT_ERR_INVALID, "bad argument");
+    if (c->last_deal_n == 0) return 0;   // the last render was dealt in raster order
+    const std::vector<uint32_t>& order = c->deal.order();
+    const int64_t m = std::min<int64_t>(n, (int64_t)order.size());
+    if (m > 0) std::memcpy(out, order.data(), (size_t)m * sizeof(uint32_t));
+    return (int)c->last_deal_n;
+}
+
 int rt_last_counters(rt_ctx* c, uint64_t* out, int n)
 {
     if (!c || !out || n < 0) return fail(RT_ERR_INVALID, "null argument");
@@ -1569,6 +1662,10 @@ int rt_ctx_set_option(rt_ctx* c, int key, int64_t v)
         c->opt.ring = (int)v;
         return RT_OK;
     case RT_OPT_COMM_DIRECT: c->opt_comm_direct = v != 0; return RT_OK;
+    case RT_OPT_AUTO_DEAL_ORDER:
+        if (v < 0 || v > 2) return fail(RT_ERR_INVALID, "deal order mode out of range (0 off, 1 auto, 2 measure only)");
+        c->opt_deal = (int)v;
+        return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
 }
@@ -1585,6 +1682,7 @@ int rt_ctx_get_option(rt_ctx* c, int key, int64_t* v)
     case RT_OPT_HOIST: *v = c->opt_hoist; return RT_OK;
     case RT_OPT_POOL_RING: *v = c->opt.ring; return RT_OK;
     case RT_OPT_COMM_DIRECT: *v = c->opt_comm_direct; return RT_OK;
+    case RT_OPT_AUTO_DEAL_ORDER: *v = c->opt_deal; return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
 }

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "ctx_internal.hpp"
+#include "deal_cache.hpp"
 #include "rt/rt_abi.h"
 #include "trace_kernel.hpp"
 
@@ -701,8 +702,7 @@ int rt_tiles_assemble_host(const void* slabs, int64_t slab_elems, int world, int
 int rt_cost_tile_order(const uint64_t* costs, int64_t n, uint32_t* order)
 {
     if (n < 0 || (n > 0 && (!costs || !order)) || n > ((int64_t)1 << 32)) return fail(RT_ERR_INVALID, "bad argument");
-    std::iota(order, order + n, 0u);
-    std::stable_sort(order, order + n, [costs](uint32_t a, uint32_t b) { return costs[a] > costs[b]; });
+    rtd::cost_order(costs, n, order);
     return RT_OK;
 }
 

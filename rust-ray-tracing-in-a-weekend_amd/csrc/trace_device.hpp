@@ -2133,6 +2133,13 @@ __device__ __forceinline__ unsigned* ring_block_id(double* ring_wave)
 // the lanes of one VGPR (profiles/r05o_ab_c{2,4}.log).
 template <class C>
 constexpr bool RingSgpr() { return C::F == FEAT_SET_SPHERES; }
+// Which pool kernels carry a whole frame's deal order and the block-cost measurement behind it
+// (KParams.tile_major = kDealOrdered / kDealMeasure, the table at kDealTable; deal_cache.hpp).
+#ifndef RT_DEAL
+#define RT_DEAL 3   // (A/B builds) bit 0: the deal order, bit 1: the block-cost measurement
+#endif
+template <class C>
+constexpr bool DealCfg() { return RT_DEAL != 0 && deal_variant(C::F) && !C::COUNT; }
 
 __device__ __forceinline__ void ring_reduce(const KParams& P, const double* __restrict__ rec,
                                             double* __restrict__ partial, unsigned blk, unsigned n_tiles, unsigned group,
@@ -2300,6 +2307,32 @@ __global__ void __launch_bounds__(BlockThreads<C>(), min_waves<C>()) trace_pool(
                     if (__builtin_expect(P.tile_major != 0, 0)) {   // (wave-uniform)
                         tile = b / P.deal_div;
                         grp = b - tile * P.deal_div;
+                        if constexpr (DealCfg<C>()) {
+                            // A whole frame's deal order: position -> raster tile through the table
+                            // behind the work counter (kDealTable), one scalar load per block off a
+                            // pointer the wave holds anyway. Everything here reads registers the
+                            // loop keeps live already (work, n_tiles, tile_major, tx0 / tk0): one
+                            // more scalar value live through the walk costs the kernel a spill in
+                            // its bounce loop (C2 +9.5 %).
+                            if (P.tile_major >= kDealOrdered) {
+                                tile = work[kDealTable + tile];
+                                if (ring) b = tile * P.deal_div + grp;   // the ring keeps the raster tile's block id
+                                // Block-cost measurement: a wave's cycles between two fetches go to
+                                // the tile of the block fetched first. No state of its own: the
+                                // previous tile is the one tx0 / tk0 still name (blk_units 0: none
+                                // yet); lane 0 adds the fetch time to that tile's cost and subtracts
+                                // it from the new tile's, so a tile's sum (mod 2^32) is its blocks'
+                                // (next fetch - own fetch); the wave's last block is closed at its end.
+                                if ((RT_DEAL & 2) && P.tile_major == kDealMeasure) {
+                                    const unsigned prev = (unsigned)(tk0 >> 3) * (unsigned)P.tiles_x + (unsigned)(tx0 >> 3);
+                                    if ((blk_units == 0 || prev != tile) && lane == 0) {
+                                        const unsigned now = (unsigned)__builtin_amdgcn_s_memtime();
+                                        if (blk_units != 0) atomicAdd(&work[kDealTable + n_tiles + prev], now);
+                                        atomicAdd(&work[kDealTable + n_tiles + tile], 0u - now);
+                                    }
+                                }
+                            }
+                        }
                     } else {
                         grp = b / n_tiles;
                         tile = b - grp * n_tiles;
@@ -2521,6 +2554,11 @@ __global__ void __launch_bounds__(BlockThreads<C>(), min_waves<C>()) trace_pool(
             }
             active = false;
         }
+    }
+    if constexpr (DealCfg<C>() && (RT_DEAL & 2) != 0) {   // the wave's last block ends with the wave
+        if (P.tile_major == kDealMeasure && blk_units != 0 && lane == 0)
+            atomicAdd(&work[kDealTable + n_tiles + (unsigned)(tk0 >> 3) * (unsigned)P.tiles_x + (unsigned)(tx0 >> 3)],
+                      (unsigned)__builtin_amdgcn_s_memtime());
     }
     if (C::COUNT) {
         atomicAdd(&counters[0], (unsigned long long)cnt.casts);

@@ -84,12 +84,25 @@ struct KParams {
     // pool schedules: work blocks dealt tile-major (all of a tile's sample groups, then the next
     // tile: set with a tile order, so the most expensive tiles are done first and entirely) rather
     // than group-major; deal_div = the block index's inner extent: tiles (group-major) or sample
-    // (chunk) groups per tile (tile-major)
+    // (chunk) groups per tile (tile-major). 2, 3 (kDealOrdered, kDealMeasure below): tile-major
+    // through a whole frame's deal table
     int32_t tile_major;
     uint32_t deal_div;
     // count_work renders (COUNT kernels): per raster tile of the image, the lane-cycles its samples took
     unsigned long long* tile_cost;
 };
+
+// KParams.tile_major beyond 1, whole-frame renders on the kernels that carry it (trace_pool,
+// DealCfg): tile-major through the deal table that follows the launch's work counter in memory,
+// work[kDealTable + position] = raster tile (records and the frame stay raster), and, measuring,
+// per raster tile the wave cycles (s_memtime, mod 2^32) between a wave's block fetches, added up at
+// work[kDealTable + tiles + tile]. They sit behind the counter, and the mode in tile_major,
+// because the kernel holds both in registers anyway.
+constexpr int32_t kDealOrdered = 2, kDealMeasure = 3;
+constexpr unsigned kDealTable = 16;   // words from the counter to the table (the counter keeps its cache line)
+// the kernel variants that carry it (trace_device.hpp, DealCfg): the spheres variants. The others
+// hold their block state at the SGPR limit (RingSgpr) and keep raster order.
+constexpr bool deal_variant(uint32_t variant) { return variant == FEAT_SET_SPHERES; }
 
 struct LaunchOpts {
     uint32_t features;  // scene features (FEAT_*)

@@ -51,6 +51,7 @@ RT_OPT_EXTRA_FEATURES = 5
 RT_OPT_HOIST = 6
 RT_OPT_POOL_RING = 9
 RT_OPT_COMM_DIRECT = 10
+RT_OPT_AUTO_DEAL_ORDER = 11   # 1 (default): whole frames dealt in self-measured cost order; 0 off; 2 measure only
 # SAH builder options (rt_world_set_build_option)
 RT_BUILD_C_ISECT = 1
 RT_BUILD_MAX_LEAF = 2
@@ -74,7 +75,7 @@ EXPORTED = [
     "rt_ctx_set_variant", "rt_device_eval", "rt_accum_create", "rt_accum_destroy", "rt_accum_add",
     "rt_accum_get", "rt_accum_set", "rt_accum_resolve", "rt_render_progressive", "rt_ctx_set_schedule", "rt_ctx_set_precision",
     "rt_scene_validate", "rt_build_info", "rt_ctx_set_option", "rt_ctx_get_option", "rt_world_set_build_option",
-    "rt_last_tile_costs", "rt_ctx_set_tile_order",
+    "rt_last_tile_costs", "rt_ctx_set_tile_order", "rt_last_deal_order",
     "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_comm_rank",
     "rt_comm_tile_order", "rt_comm_tile_order_all", "rt_render_gather", "rt_render_gather_all",
     "rt_comm_last_stats", "rt_tiles_assemble", "rt_tiles_assemble_host", "rt_cost_tile_order",
@@ -249,6 +250,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_tiles_in_shard": ([I, I, I, I], I), "rt_last_stats": ([P, ctypes.POINTER(Stats)], I),
         "rt_last_counters": ([P, P, I], I),
         "rt_last_tile_costs": ([P, P, ctypes.c_int64], I), "rt_ctx_set_tile_order": ([P, P, ctypes.c_int64], I),
+        "rt_last_deal_order": ([P, P, ctypes.c_int64], I),
         "rt_write_ppm": ([P, I, I, ctypes.c_char_p], I),
         "rt_write_ppm_f64": ([P, I, I, I, ctypes.c_char_p], I),
         "rt_write_color": ([P, I, ctypes.c_int64, P], I),
@@ -820,6 +822,17 @@ class Renderer:
         out = np.zeros(n, dtype=np.uint64)
         if n:
             _check(min(0, self.lib.rt_last_tile_costs(self.h, out.ctypes.data, n)), "rt_last_tile_costs")
+        return out
+
+    def deal_order(self) -> np.ndarray:
+        """The cost order the last render's work blocks were dealt in (rt_last_deal_order,
+        RT_OPT_AUTO_DEAL_ORDER): position -> raster tile; empty if it was dealt in raster order."""
+        n = self.lib.rt_last_deal_order(self.h, None, 0)
+        if n < 0:
+            _check(n, "rt_last_deal_order")
+        out = np.zeros(n, dtype=np.uint32)
+        if n:
+            _check(min(0, self.lib.rt_last_deal_order(self.h, out.ctypes.data, n)), "rt_last_deal_order")
         return out
 
     def set_tile_order(self, order=None):
