@@ -30,6 +30,9 @@
  *                             (main.rs:516) decided per 8x8 tile from the estimate's noise
  *   rt_denoise                (new) a post-filter over the adaptive frame and its noise map; the
  *                             reference has no filter
+ *   rt_render_features        (new) the first hit of the same primary rays (camera.rs:58-66) as
+ *                             albedo, normal and depth buffers; the reference writes none
+ *   rt_denoise_guided         (new) rt_denoise with those buffers in its weights
  *
  * Threading: a context is bound to one device and is used by one host thread at
  * a time. Worlds are plain host objects.
@@ -542,6 +545,86 @@ typedef struct rt_denoise_stats {
     int32_t reserved0;
 } rt_denoise_stats;
 int rt_denoise_last_stats(rt_ctx* ctx, rt_denoise_stats* out);
+
+/* ---- first-hit feature buffers (additive to ABI v6: new symbols only) ---------------------------
+ * The auxiliary buffers a denoiser takes beside the colour: per pixel the mean, over the pixel's
+ * p->spp samples, of the first hit's albedo, normal and depth. One GPU, whole frames, f64.
+ *
+ * Which ray. For every pixel and every sample s in [0, p->spp) the primary ray is exactly the one
+ * rt_render shoots for (pixel, s) under p->render_seed: the same path stream and the same camera
+ * ray, pixel jitter, lens draw and time draw included. It is cast once, as rt_render's first
+ * bounce is (t_min = 0.001, the medium's draw keyed by bounce 0, so fog is hit where rt_render's
+ * path hits it). Nothing scatters, no scatter value is drawn and no second ray is cast.
+ *
+ * What a sample contributes.
+ *   albedo  the first hit's material colour at the hit record (its u, v, p): Lambertian and
+ *           Isotropic their texture value (the attenuation their scatter returns), DiffuseLight
+ *           its emitted texture value, Metal its albedo, Dielectric (1, 1, 1); a miss
+ *           p->background
+ *   normal  the hit record's world-space normal as the material sees it: against the ray
+ *           (set_face_normal), mapped back through translate / rotate_y as the reference maps it;
+ *           a constant medium's hit keeps the record's normal; a miss (0, 0, 0)
+ *   depth   sqrt((ex ex + ey ey) + ez ez), e = the hit point - the ray's origin; a miss 0
+ * Sums. Every channel is sum * (1 / p->spp), the sum associated as rt_render's: chunk sums from
+ * 0.0 in sample order, added in chunk order to 0.0; the chunk is p->spp_chunk, or rt_render's
+ * automatic chunk for p->spp. Every draw is keyed by (pixel, sample), so the bits depend on
+ * neither the launch geometry nor the acceleration structure nor the kernel variant. A mean
+ * normal is shorter than 1 where the samples' normals differ.
+ *
+ * p: spp >= 1; max_depth, count_work and out_format are ignored; the shard fields (row_begin,
+ * row_stride other than 0 / 1, row_block > 1, tile_shard) must be unset (RT_ERR_INVALID). No
+ * uploaded scene: RT_ERR_NO_SCENE. RT_PREC_F32 contexts: RT_ERR_UNSUPPORTED. Host pointers: the
+ * call is synchronous. With p->out_on_device the outputs are device pointers and the call is only
+ * enqueued on p->stream (or the context's stream), like rt_render.
+ * The kernel is trace_features (one instantiation per kernel variant, picked by the scene's
+ * features and RT_OPT_EXTRA_FEATURES as rt_render's); chunk partials beyond
+ * RT_OPT_TRACE_BUF_BYTES are taken in batches on chunk boundaries, same bits. */
+typedef struct rt_features_out {      /* all f64, row 0 = bottom; at least one non-NULL */
+    double* albedo;   /* height x width x 3, or NULL */
+    double* normal;   /* height x width x 3, or NULL */
+    double* depth;    /* height x width,     or NULL */
+} rt_features_out;
+int rt_render_features(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p, const rt_features_out* out);
+
+typedef struct rt_features_stats {
+    double kernel_ms, reduce_ms;   /* last rt_render_features: its trace_features launches, its reductions
+                                      (HIP events; waits for them if the call was only enqueued) */
+    uint64_t samples;              /* width x height x spp */
+    int32_t variant_features;      /* the kernel variant's feature set, as rt_stats.variant_features */
+    int32_t spp_chunk;
+} rt_features_stats;
+int rt_features_last_stats(rt_ctx* ctx, rt_features_stats* out);
+
+/* ---- feature-guided NL-means (additive to ABI v6: new symbols only) -----------------------------
+ * rt_denoise with its weight multiplied by a feature term, so a texture or geometry edge the
+ * colour distance cannot tell from noise stays sharp. The filter is rt_denoise's in every respect
+ * (D, the raster order of the offsets, the finite-value rules, out(p) = M(p) where Y(p) or V(p)
+ * is not finite) except for the weight. Guides: A (albedo) and N (normal), height x width x 3 f64,
+ * Z (depth), height x width f64, as rt_render_features writes them; each may be NULL. For a pixel
+ * p and q = p + o, per pixel pair (not summed over the patch):
+ *   a_i = A_i(p) - A_i(q);  dA = (a_0 a_0 + a_1 a_1) + a_2 a_2        (dN the same over N)
+ *   z   = Z(p) - Z(q);      dZ = z z / (1e-10 + (Z(p) Z(p) + Z(q) Z(q)))
+ *   Phi(p, o) = dA ia + dN in + dZ iz, left to right; ia = 1 / (sigma_albedo sigma_albedo) etc.,
+ *               computed once on the host in f64; the term of a NULL guide is skipped
+ *   w(p, o)   = exp(-(max(0, D(p, o)) + Phi(p, o))) if D and Phi are finite, otherwise 0;
+ *               w(p, (0,0)) = 1
+ * All arithmetic is f64 with no contraction. A NaN or Inf feature value at q therefore removes
+ * the pairs that touch q and nothing else. g == NULL, or all three guides NULL, is rt_denoise bit
+ * for bit (rt_denoise is this entry without guides). The guides are device pointers iff
+ * p->on_device. RT_ERR_INVALID as rt_denoise, and for a non-NULL guide whose sigma is not greater
+ * than 0 and finite; the sigma of a NULL guide is ignored. Albedo demodulation (filtering
+ * colour / albedo) is not part of it. rt_denoise_last_stats reports a guided call as a plain one. */
+typedef struct rt_denoise_guides {
+    const double* albedo;   /* height x width x 3 or NULL */
+    const double* normal;   /* height x width x 3 or NULL */
+    const double* depth;    /* height x width or NULL */
+    double sigma_albedo, sigma_normal, sigma_depth;   /* > 0 and finite for every non-NULL guide */
+} rt_denoise_guides;
+int rt_denoise_guided(rt_ctx* ctx, const rt_denoise_params* p, const void* mean, const double* stderr_map,
+                      const rt_denoise_guides* g, void* out);
+/* The same filter on the host, no device needed (on_device and stream are ignored). */
+int rt_denoise_guided_host(const rt_denoise_params* p, const void* mean, const double* stderr_map,
+                           const rt_denoise_guides* g, void* out);
 
 /* ---- output ------------------------------------------------------------------------------ */
 /* P3 PPM byte for byte as the reference writes it (write_color, math.rs:119-132; main.rs:472,

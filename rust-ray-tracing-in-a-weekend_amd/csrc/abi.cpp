@@ -18,6 +18,7 @@
 #include "ctx_internal.hpp"
 #include "deal_cache.hpp"
 #include "denoise.hpp"
+#include "features_kernel.hpp"
 #include "launch_plan.hpp"
 #include "scene_lower.hpp"
 #include "scene_model.hpp"
@@ -88,6 +89,9 @@ struct rt_ctx {
     rt_denoise_stats dstats{};          // the last rt_denoise (rt_denoise_last_stats)
     hipEvent_t ev_dn[2] = {nullptr, nullptr};   // around its kernel
     bool pending_dn = false;            // its kernel_ms is still to be read from the events
+    rt_features_stats fstats{};         // the last rt_render_features (rt_features_last_stats)
+    hipEvent_t ev_ft[3] = {nullptr, nullptr, nullptr};   // before its trace launches, after them, after its reductions
+    bool pending_ft = false;            // its times are still to be read from the events
     // what a render's launch plan is made from (launch_plan.hpp): the uploaded scene, the device, the switches
     rtp::SceneFacts scene;
     rtp::DeviceFacts dev;
@@ -191,6 +195,7 @@ int rt_ctx_create(int device, rt_ctx** out)
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->ev_rd[i], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev_dn[i]);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev_ft[i]);
     if (e != hipSuccess) {
         rt_ctx_destroy(c);
         return hip_fail(e, "rt_ctx_create");
@@ -226,6 +231,8 @@ void rt_ctx_destroy(rt_ctx* c)
     }
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
     for (auto& e : c->ev_dn)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->ev_ft)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1394,6 +1401,139 @@ int rt_adaptive_last_stats(rt_ctx* c, rt_adaptive_stats* out)
     return RT_OK;
 }
 
+// ---- first-hit feature buffers (rt_abi.h; features_device.hpp, features_kernel.hip) -------------
+// The launch is the chunk schedule's, planned as one (rtp::plan with the schedule set to CHUNKS:
+// the kernel variant, the slab precision, what is staged in LDS), on the context's trace-output
+// buffer: 7 doubles per (pixel, chunk), in batches on chunk boundaries when they exceed the
+// buffer's bound, the running sums then carried in acc_tmp. Events: ev_ft[0] before the first
+// trace_features launch, ev_ft[1] after the last one, ev_ft[2] after the last reduction.
+int rt_render_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_features_out* out)
+{
+    if (!c || !cam || !p || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (!out->albedo && !out->normal && !out->depth) return fail(RT_ERR_INVALID, "rt_features_out: every output is null");
+    if (!c->has_scene) return fail(RT_ERR_NO_SCENE, "no scene uploaded");
+    if (p->row_begin != 0 || (p->row_stride != 0 && p->row_stride != 1) || p->row_block < 0 || p->row_block > 1 ||
+        p->tile_shard != 0)
+        return fail(RT_ERR_INVALID, "rt_render_features renders whole frames: the shard fields must be unset");
+    rt_render_params rp = *p;
+    rp.row_stride = 1;
+    rp.row_block = 0;
+    rp.count_work = 0;
+    if (bad_geometry(&rp) || p->spp < 1) return fail(RT_ERR_INVALID, "bad render params (rt_render_features needs spp >= 1)");
+    if (c->opt.precision == RT_PREC_F32) return fail(RT_ERR_UNSUPPORTED, "feature buffers in the f32 mode");
+    const Layout lay = layout_of(&rp);
+    const int W = p->width, H = p->height;
+    if (lay.w != W || lay.rows != H) return fail(RT_ERR_INVALID, "bad render params");
+    const long long n_px = (long long)W * H;
+    const int chunk = p->spp_chunk > 0 ? std::min(p->spp_chunk, p->spp) : auto_chunk(p->spp);
+    const int n_chunks = (p->spp + chunk - 1) / chunk;
+    const bool on_dev = p->out_on_device != 0;
+
+    rtp::Options opt = c->opt;
+    opt.schedule = RT_SCHED_CHUNKS;
+    rtp::Request rq;
+    rq.lay = lay;
+    rq.s_begin = 0;
+    rq.s_end = p->spp;
+    rq.chunk = chunk;
+    rq.cam_mag = rtp::camera_magnitude(*cam);
+    const rtp::Plan pl = rtp::plan(c->scene, c->dev, opt, rq, rtp::Retry{c->sample_buf_cap, false});
+    if (pl.err) return fail(pl.err, pl.err_msg);
+
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = p->stream ? (hipStream_t)p->stream : c->stream;
+    StreamScope scope(c, stream);
+    int rc = scope.begin();
+    if (rc) return rc;
+
+    // chunks per batch: what the trace-output bound holds (at least one)
+    const size_t chunk_bytes = (size_t)n_px * rtk::kFeatureChannels * sizeof(double);
+    const int batch = (int)std::min<size_t>((size_t)n_chunks, std::max<size_t>(1, c->sample_buf_cap / chunk_bytes));
+    const int n_batches = (n_chunks + batch - 1) / batch;
+    rc = grow(c, stream, c->partial, c->partial_cap, (size_t)batch * chunk_bytes);
+    if (rc) return rc;
+    if (n_batches > 1) {
+        rc = grow(c, stream, c->acc_tmp, c->acc_tmp_cap, chunk_bytes);
+        if (rc) return rc;
+    }
+    // host-bound frames: staged [albedo | normal | depth] in the context's output buffer
+    const size_t px = (size_t)n_px;
+    double *d_albedo = out->albedo, *d_normal = out->normal, *d_depth = out->depth;
+    if (!on_dev) {
+        void* stage = nullptr;
+        rc = out_staging(c, stream, 7 * px * sizeof(double), stage);
+        if (rc) return rc;
+        double* s = (double*)stage;
+        d_albedo = out->albedo ? s : nullptr;
+        d_normal = out->normal ? s + 3 * px : nullptr;
+        d_depth = out->depth ? s + 6 * px : nullptr;
+    }
+
+    const int64_t img_tiles = (int64_t)((W + 7) / 8) * ((H + 7) / 8);
+    rtk::KParams K;
+    rc = fill_kparams(c, cam, &rp, lay, chunk, Sink{}, img_tiles, K);
+    if (rc) return rc;
+    rtk::SceneDev S = c->S;
+    S.n_lds_nodes = pl.n_lds_nodes;
+    S.n_lds_materials = pl.n_lds_materials;
+    S.n_lds_textures = pl.n_lds_textures;
+    S.n_lds_blas = pl.n_lds_blas;
+    rtk::LaunchOpts o;
+    o.features = pl.features;
+    o.slab32 = pl.slab32;
+    o.lds_stack = pl.lds_stack;
+    o.count = 0;
+    o.pool = RT_SCHED_CHUNKS;
+    o.f32 = 0;
+
+    HIP_TRY(hipEventRecord(c->ev_ft[0], stream));
+    for (int bi = 0; bi < n_batches; ++bi) {
+        const int c0 = bi * batch, c1 = std::min(n_chunks, c0 + batch);
+        K.sample_begin = c0 * chunk;
+        K.spp = (int)std::min<long long>(p->spp, (long long)c1 * chunk);
+        K.n_chunks = c1 - c0;
+        rtk::KParams* dK = c->params + c->param_slot;
+        c->param_slot = (c->param_slot + 1) % kParamSlots;
+        HIP_TRY(hipMemcpyAsync(dK, &K, sizeof K, hipMemcpyHostToDevice, stream));
+        HIP_TRY(rtk::launch_features(S, K, dK, c->partial, o, stream));
+        if (bi == n_batches - 1) HIP_TRY(hipEventRecord(c->ev_ft[1], stream));
+        HIP_TRY(rtk::launch_reduce_features(c->partial, c->acc_tmp, d_albedo, d_normal, d_depth, n_px, K.n_chunks, bi == 0,
+                                            bi == n_batches - 1, 1.0 / (double)p->spp, stream));
+    }
+    HIP_TRY(hipEventRecord(c->ev_ft[2], stream));
+    c->fstats = rt_features_stats{};
+    c->fstats.samples = (uint64_t)n_px * (uint64_t)p->spp;
+    c->fstats.variant_features = (int32_t)pl.variant;
+    c->fstats.spp_chunk = chunk;
+    c->pending_ft = true;
+    if (!on_dev) {
+        if (out->albedo) HIP_TRY(hipMemcpyAsync(out->albedo, d_albedo, 3 * px * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (out->normal) HIP_TRY(hipMemcpyAsync(out->normal, d_normal, 3 * px * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (out->depth) HIP_TRY(hipMemcpyAsync(out->depth, d_depth, px * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    rc = scope.end();
+    if (rc) return rc;
+    if (!on_dev) HIP_TRY(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+int rt_features_last_stats(rt_ctx* c, rt_features_stats* out)
+{
+    if (!c || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (c->pending_ft) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipEventSynchronize(c->ev_ft[2]));
+        float a = 0, b = 0;
+        HIP_TRY(hipEventElapsedTime(&a, c->ev_ft[0], c->ev_ft[1]));
+        HIP_TRY(hipEventElapsedTime(&b, c->ev_ft[1], c->ev_ft[2]));
+        c->fstats.kernel_ms = a;
+        c->fstats.reduce_ms = b;
+        c->pending_ft = false;
+    }
+    *out = c->fstats;
+    return RT_OK;
+}
+
 // ---- variance-guided NL-means (rt_abi.h: the filter; denoise_kernel.hip; denoise_host.cpp) -------
 namespace {
 // rt_denoise_host lives in denoise_host.cpp, which links without this file: its error text comes
@@ -1401,10 +1541,13 @@ namespace {
 [[maybe_unused]] const bool g_denoise_sink_set =(rtk::denoise_error_sink = [](const char* msg) { g_last_error = msg; }, true);
 }  // namespace
 
-int rt_denoise(rt_ctx* c, const rt_denoise_params* p, const void* mean, const double* stderr_map, void* out)
+int rt_denoise_guided(rt_ctx* c, const rt_denoise_params* p, const void* mean, const double* stderr_map,
+                      const rt_denoise_guides* g, void* out)
 {
     if (!c) return fail(RT_ERR_INVALID, "null argument");
     if (const char* bad = rtk::denoise_check(p, mean, stderr_map, out)) return fail(RT_ERR_INVALID, bad);
+    rtk::DenoiseGuides G;
+    if (const char* bad = rtk::denoise_guides_check(g, G)) return fail(RT_ERR_INVALID, bad);
     const bool f64 = p->format == RT_OUT_F64, on_dev = p->on_device != 0;
     const size_t hw = (size_t)p->width * (size_t)p->height;
     const size_t frame_bytes = hw * 3 * (f64 ? 8 : 4), se_bytes = hw * sizeof(double);
@@ -1415,22 +1558,35 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* p, const void* mean, const do
     int rc = scope.begin();
     if (rc) return rc;
 
-    // host pointers: the frame, the map and the result staged in one device block of the call's own
+    // host pointers: the frame, the map, the result and the guides staged in one device block of the call's own
     DeviceBlock blk;
     const void* d_mean = mean;
     const double* d_se = stderr_map;
     void* d_out = out;
     if (!on_dev) {
         const size_t off_se = align_up(frame_bytes, 256), off_out = off_se + align_up(se_bytes, 256);
-        HIP_TRY(hipMalloc(&blk.p, off_out + frame_bytes));
+        const size_t g3 = align_up(hw * 3 * sizeof(double), 256), g1 = align_up(se_bytes, 256);
+        const size_t off_ga = off_out + align_up(frame_bytes, 256), off_gn = off_ga + (G.albedo ? g3 : 0);
+        const size_t off_gz = off_gn + (G.normal ? g3 : 0);
+        HIP_TRY(hipMalloc(&blk.p, off_gz + (G.depth ? g1 : 0) + 256));
         d_mean = blk.p;
         d_se = (const double*)((char*)blk.p + off_se);
         d_out = (char*)blk.p + off_out;
         HIP_TRY(hipMemcpyAsync(blk.p, mean, frame_bytes, hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemcpyAsync((void*)d_se, stderr_map, se_bytes, hipMemcpyHostToDevice, stream));
+        auto stage = [&](const double*& guide, size_t off, size_t bytes) {
+            if (!guide) return hipSuccess;
+            void* d = (char*)blk.p + off;
+            const hipError_t e = hipMemcpyAsync(d, guide, bytes, hipMemcpyHostToDevice, stream);
+            guide = (const double*)d;
+            return e;
+        };
+        HIP_TRY(stage(G.albedo, off_ga, hw * 3 * sizeof(double)));
+        HIP_TRY(stage(G.normal, off_gn, hw * 3 * sizeof(double)));
+        HIP_TRY(stage(G.depth, off_gz, se_bytes));
     }
     HIP_TRY(hipEventRecord(c->ev_dn[0], stream));
-    HIP_TRY(rtk::launch_denoise(d_mean, d_se, d_out, f64, p->width, p->height, p->radius, p->patch, p->k, stream));
+    HIP_TRY(rtk::launch_denoise(d_mean, d_se, d_out, f64, p->width, p->height, p->radius, p->patch, p->k, G, stream));
     HIP_TRY(hipEventRecord(c->ev_dn[1], stream));
     c->dstats = rt_denoise_stats{};
     c->dstats.radius = p->radius;
@@ -1442,6 +1598,12 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* p, const void* mean, const do
     if (rc) return rc;
     if (!on_dev) HIP_TRY(hipStreamSynchronize(stream));   // (the block is freed once its copies are done)
     return RT_OK;
+}
+
+// the guided filter with no guides
+int rt_denoise(rt_ctx* c, const rt_denoise_params* p, const void* mean, const double* stderr_map, void* out)
+{
+    return rt_denoise_guided(c, p, mean, stderr_map, nullptr, out);
 }
 
 int rt_denoise_last_stats(rt_ctx* c, rt_denoise_stats* out)

@@ -1,5 +1,6 @@
-// denoise_host.cpp — rt_denoise_host: the variance-guided NL-means filter of include/rt/rt_abi.h
-// on the host, with denoise_core.hpp's arithmetic (the device kernel's). Plain C++: no HIP, and
+// denoise_host.cpp — rt_denoise_host and rt_denoise_guided_host: the variance-guided NL-means
+// filter of include/rt/rt_abi.h, without and with feature guides, on the host, with
+// denoise_core.hpp's arithmetic (the device kernel's). Plain C++: no HIP, and
 // nothing from the rest of the library, so a test program can link this file alone.
 #include <cmath>
 #include <new>
@@ -25,6 +26,22 @@ const char* denoise_check(const rt_denoise_params* p, const void* mean, const do
     return nullptr;
 }
 
+const char* denoise_guides_check(const rt_denoise_guides* g, DenoiseGuides& G)
+{
+    G = DenoiseGuides{};
+    if (!g) return nullptr;
+    auto bad = [](double s) { return !(s > 0.0) || !denoise_finite(s); };
+    if ((g->albedo && bad(g->sigma_albedo)) || (g->normal && bad(g->sigma_normal)) || (g->depth && bad(g->sigma_depth)))
+        return "the sigma of every guide given must be greater than 0 and finite";
+    G.albedo = g->albedo;
+    G.normal = g->normal;
+    G.depth = g->depth;
+    if (g->albedo) G.ia = 1.0 / (g->sigma_albedo * g->sigma_albedo);
+    if (g->normal) G.in = 1.0 / (g->sigma_normal * g->sigma_normal);
+    if (g->depth) G.iz = 1.0 / (g->sigma_depth * g->sigma_depth);
+    return nullptr;
+}
+
 namespace {
 
 int denoise_fail(int code, const char* msg)
@@ -34,8 +51,9 @@ int denoise_fail(int code, const char* msg)
 }
 
 template <typename T>
-void filter(const rt_denoise_params& p, const T* M, const double* se, T* out)
+void filter(const rt_denoise_params& p, const T* M, const double* se, const DenoiseGuides& G, T* out)
 {
+    const bool guided = G.any();
     const int W = p.width, H = p.height, r = p.radius, f = p.patch;
     const size_t hw = (size_t)W * (size_t)H;
     const double k2 = p.k * p.k;
@@ -63,16 +81,17 @@ void filter(const rt_denoise_params& p, const T* M, const double* se, T* out)
             for (int y = y0; y < y1; ++y) {
                 const int sy0 = y - f > y0 ? y - f : y0, sy1 = y + f < y1 - 1 ? y + f : y1 - 1;
                 for (int x = x0; x < x1; ++x) {
+                    const size_t a = (size_t)y * W + x, b = (size_t)(y + dy) * W + (x + dx);
                     double w = 1.0;
                     if (!centre) {
                         const int sx0 = x - f > x0 ? x - f : x0, sx1 = x + f < x1 - 1 ? x + f : x1 - 1;
                         double s = 0.0;
                         for (int sy = sy0; sy <= sy1; ++sy)
                             for (int sx = sx0; sx <= sx1; ++sx) s = s + delta[(size_t)sy * W + sx];
-                        w = denoise_weight(s / (double)((sx1 - sx0 + 1) * (sy1 - sy0 + 1)));
+                        const double D = s / (double)((sx1 - sx0 + 1) * (sy1 - sy0 + 1));
+                        w = guided ? denoise_weight_guided(D, denoise_phi(G, a, b)) : denoise_weight(D);
                     }
                     if (w == 0.0) continue;
-                    const size_t a = (size_t)y * W + x, b = (size_t)(y + dy) * W + (x + dx);
                     num[3 * a + 0] = num[3 * a + 0] + w * (double)M[3 * b + 0];
                     num[3 * a + 1] = num[3 * a + 1] + w * (double)M[3 * b + 1];
                     num[3 * a + 2] = num[3 * a + 2] + w * (double)M[3 * b + 2];
@@ -90,14 +109,23 @@ void filter(const rt_denoise_params& p, const T* M, const double* se, T* out)
 }  // namespace
 }  // namespace rtk
 
-extern "C" int rt_denoise_host(const rt_denoise_params* p, const void* mean, const double* stderr_map, void* out)
+extern "C" int rt_denoise_guided_host(const rt_denoise_params* p, const void* mean, const double* stderr_map,
+                                      const rt_denoise_guides* g, void* out)
 {
     if (const char* bad = rtk::denoise_check(p, mean, stderr_map, out)) return rtk::denoise_fail(RT_ERR_INVALID, bad);
+    rtk::DenoiseGuides G;
+    if (const char* bad = rtk::denoise_guides_check(g, G)) return rtk::denoise_fail(RT_ERR_INVALID, bad);
     try {
-        if (p->format == RT_OUT_F64) rtk::filter<double>(*p, (const double*)mean, stderr_map, (double*)out);
-        else rtk::filter<float>(*p, (const float*)mean, stderr_map, (float*)out);
+        if (p->format == RT_OUT_F64) rtk::filter<double>(*p, (const double*)mean, stderr_map, G, (double*)out);
+        else rtk::filter<float>(*p, (const float*)mean, stderr_map, G, (float*)out);
     } catch (const std::bad_alloc&) {
         return rtk::denoise_fail(RT_ERR_OOM, "rt_denoise_host: frame-sized work arrays");
     }
     return RT_OK;
+}
+
+// the guided filter with no guides
+extern "C" int rt_denoise_host(const rt_denoise_params* p, const void* mean, const double* stderr_map, void* out)
+{
+    return rt_denoise_guided_host(p, mean, stderr_map, nullptr, out);
 }

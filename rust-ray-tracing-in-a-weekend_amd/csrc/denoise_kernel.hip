@@ -18,6 +18,11 @@
 // rows of 16 pixels, and a row stride of 16 mod 32 doubles puts them on all 64 banks once.
 // No atomics and no cross-workgroup state: a pixel's sums depend on the frame alone, in raster
 // offset order, whatever the tiling, so the result repeats bit for bit.
+//
+// rt_denoise_guided is the same kernel with G set: the weight takes denoise_core.hpp's feature
+// term Phi(p, o) as well, from the guide frames' values at p and at q = p + o, read from global
+// memory beside M(q) (frame-sized f64 arrays, L2-resident at these sizes; nothing more in LDS).
+// The instantiation without guides holds none of it.
 #include "denoise.hpp"
 #include "denoise_core.hpp"
 
@@ -27,11 +32,11 @@ constexpr int kDenoiseTile = 16;
 
 __host__ __device__ constexpr int denoise_plane_stride(int patch) { return patch == 0 ? 16 : 48; }
 
-template <typename T, int F>
+template <typename T, int F, bool G>
 __global__ void __launch_bounds__(kDenoiseTile * kDenoiseTile) denoise_nlm(const T* __restrict__ M,
                                                                           const double* __restrict__ se,
                                                                           T* __restrict__ out, int W, int H, int tiles_x,
-                                                                          int r, double k2)
+                                                                          int r, double k2, DenoiseGuides guides)
 {
     extern __shared__ double lds[];
     constexpr int kThreads = kDenoiseTile * kDenoiseTile;
@@ -90,7 +95,12 @@ __global__ void __launch_bounds__(kDenoiseTile * kDenoiseTile) denoise_nlm(const
 #pragma unroll
                     for (int sx = 0; sx <= 2 * F; ++sx) s = s + pl[(ly + sy) * PS + lx + sx];
                 }
-                w = denoise_weight(s / (double)(denoise_axis_count(px, dx, F, W) * cnt_y));
+                const double D = s / (double)(denoise_axis_count(px, dx, F, W) * cnt_y);
+                if constexpr (G)
+                    w = denoise_weight_guided(D, denoise_phi(guides, (size_t)py * (size_t)W + (size_t)px,
+                                                             (size_t)qy * (size_t)W + (size_t)qx));
+                else
+                    w = denoise_weight(D);
             }
             if (w == 0.0) continue;
             const size_t b = (size_t)qy * (size_t)W + (size_t)qx;
@@ -120,39 +130,42 @@ int denoise_lds_bytes(int radius, int patch)
     return (2 * sw * sw + 2 * pw * denoise_plane_stride(patch)) * (int)sizeof(double);
 }
 
-template <typename T, int F>
+template <typename T, int F, bool G>
 static hipError_t launch_one(const void* mean, const double* se, void* out, int width, int height, int radius,
-                             double k, hipStream_t stream)
+                             double k, const DenoiseGuides& guides, hipStream_t stream)
 {
     const int tiles_x = (width + kDenoiseTile - 1) / kDenoiseTile, tiles_y = (height + kDenoiseTile - 1) / kDenoiseTile;
     const long long tiles = (long long)tiles_x * tiles_y;
     if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((denoise_nlm<T, F>), dim3((unsigned)tiles), dim3(kDenoiseTile * kDenoiseTile),
+    hipLaunchKernelGGL((denoise_nlm<T, F, G>), dim3((unsigned)tiles), dim3(kDenoiseTile * kDenoiseTile),
                        (size_t)denoise_lds_bytes(radius, F), stream, (const T*)mean, se, (T*)out, width, height, tiles_x,
-                       radius, k * k);
+                       radius, k * k, guides);
     return hipGetLastError();
 }
 
-template <typename T>
+template <typename T, bool G>
 static hipError_t launch_patch(const void* mean, const double* se, void* out, int width, int height, int radius,
-                               int patch, double k, hipStream_t stream)
+                               int patch, double k, const DenoiseGuides& guides, hipStream_t stream)
 {
     switch (patch) {
-    case 0: return launch_one<T, 0>(mean, se, out, width, height, radius, k, stream);
-    case 1: return launch_one<T, 1>(mean, se, out, width, height, radius, k, stream);
-    case 2: return launch_one<T, 2>(mean, se, out, width, height, radius, k, stream);
-    case 3: return launch_one<T, 3>(mean, se, out, width, height, radius, k, stream);
+    case 0: return launch_one<T, 0, G>(mean, se, out, width, height, radius, k, guides, stream);
+    case 1: return launch_one<T, 1, G>(mean, se, out, width, height, radius, k, guides, stream);
+    case 2: return launch_one<T, 2, G>(mean, se, out, width, height, radius, k, guides, stream);
+    case 3: return launch_one<T, 3, G>(mean, se, out, width, height, radius, k, guides, stream);
     }
     return hipErrorInvalidValue;
 }
 
 hipError_t launch_denoise(const void* mean, const double* se, void* out, bool f64, int width, int height, int radius,
-                          int patch, double k, hipStream_t stream)
+                          int patch, double k, const DenoiseGuides& guides, hipStream_t stream)
 {
     if (width < 1 || height < 1 || radius < 1 || radius > kDenoiseMaxRadius || patch < 0 || patch > kDenoiseMaxPatch)
         return hipErrorInvalidValue;
-    return f64 ? launch_patch<double>(mean, se, out, width, height, radius, patch, k, stream)
-               : launch_patch<float>(mean, se, out, width, height, radius, patch, k, stream);
+    if (guides.any())
+        return f64 ? launch_patch<double, true>(mean, se, out, width, height, radius, patch, k, guides, stream)
+                   : launch_patch<float, true>(mean, se, out, width, height, radius, patch, k, guides, stream);
+    return f64 ? launch_patch<double, false>(mean, se, out, width, height, radius, patch, k, guides, stream)
+               : launch_patch<float, false>(mean, se, out, width, height, radius, patch, k, guides, stream);
 }
 
 }  // namespace rtk

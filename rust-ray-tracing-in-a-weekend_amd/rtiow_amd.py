@@ -81,6 +81,7 @@ EXPORTED = [
     "rt_comm_last_stats", "rt_tiles_assemble", "rt_tiles_assemble_host", "rt_cost_tile_order",
     "rt_render_adaptive", "rt_adaptive_last_stats", "rt_adaptive_tile_errors_host",
     "rt_denoise", "rt_denoise_host", "rt_denoise_last_stats",
+    "rt_render_features", "rt_features_last_stats", "rt_denoise_guided", "rt_denoise_guided_host",
 ]
 
 # int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_total)
@@ -205,6 +206,31 @@ class DenoiseStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FeaturesOut(ctypes.Structure):
+    """rt_features_out: any may be null, not all."""
+    _fields_ = [("albedo", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("depth", ctypes.c_void_p)]
+
+
+class FeaturesStats(ctypes.Structure):
+    """rt_features_stats: the last rt_render_features of a context."""
+    _fields_ = [("kernel_ms", ctypes.c_double), ("reduce_ms", ctypes.c_double), ("samples", ctypes.c_uint64),
+                ("variant_features", ctypes.c_int32), ("spp_chunk", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DenoiseGuides(ctypes.Structure):
+    """rt_denoise_guides: the guide frames (any may be null) and their sigmas."""
+    _fields_ = [("albedo", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("depth", ctypes.c_void_p),
+                ("sigma_albedo", ctypes.c_double), ("sigma_normal", ctypes.c_double), ("sigma_depth", ctypes.c_double)]
+
+
+# rt_denoise_guided's default sigmas (albedo, normal, depth): the lowest RMSE of the sweep over
+# {0.05, 0.1, 0.2, 0.4}^3 on C2 at threshold 0.02 with (10, 3, 0.45), guides at 16 spp; the
+# loosest corner of that grid (DESIGN.md 5.10, profiles/guided_sweep_c2.json)
+GUIDE_SIGMAS = (0.4, 0.4, 0.4)
+
 _lib = None
 
 
@@ -282,6 +308,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_denoise": ([P, ctypes.POINTER(DenoiseParams), P, P, P], I),
         "rt_denoise_host": ([ctypes.POINTER(DenoiseParams), P, P, P], I),
         "rt_denoise_last_stats": ([P, ctypes.POINTER(DenoiseStats)], I),
+        "rt_render_features": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
+                                ctypes.POINTER(FeaturesOut)], I),
+        "rt_features_last_stats": ([P, ctypes.POINTER(FeaturesStats)], I),
+        "rt_denoise_guided": ([P, ctypes.POINTER(DenoiseParams), P, P, ctypes.POINTER(DenoiseGuides), P], I),
+        "rt_denoise_guided_host": ([ctypes.POINTER(DenoiseParams), P, P, ctypes.POINTER(DenoiseGuides), P], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name, None)
@@ -623,6 +654,42 @@ def denoise_host(mean, se, radius: int = 10, patch: int = 3, k: float = 0.45) ->
     return out
 
 
+def _guide_args(shape, albedo, normal, depth, sigmas):
+    """(rt_denoise_guides, the arrays it points into) of a host-pointer guided call: albedo and normal
+    height x width x 3, depth height x width, f64; None leaves a guide out."""
+    H, W = shape
+    keep = []
+
+    def arr(a, want, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != want:
+            raise RTError(f"denoise_guided: the {name} guide is {a.shape}, not {want}")
+        keep.append(a)
+        return a.ctypes.data
+
+    sa, sn, sz = (float(v) for v in sigmas)
+    g = DenoiseGuides(arr(albedo, (H, W, 3), "albedo"), arr(normal, (H, W, 3), "normal"), arr(depth, (H, W), "depth"),
+                      sa, sn, sz)
+    return g, keep
+
+
+def denoise_guided_host(mean, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS, radius: int = 10,
+                        patch: int = 3, k: float = 0.45) -> np.ndarray:
+    """rt_denoise_guided_host: the feature-guided NL-means filter (rt_abi.h) on the host, no device
+    needed. mean and se as denoise_host; albedo, normal (height x width x 3) and depth (height x
+    width) as render_features returns them, None to leave one out; sigmas = (albedo, normal, depth)."""
+    lib = load_library()
+    p, m, s = _denoise_args(mean, se, radius, patch, k)
+    g, keep = _guide_args(m.shape[:2], albedo, normal, depth, sigmas)
+    out = np.empty_like(m)
+    _check(lib.rt_denoise_guided_host(ctypes.byref(p), m.ctypes.data, s.ctypes.data, ctypes.byref(g), out.ctypes.data),
+           "rt_denoise_guided_host")
+    del keep
+    return out
+
+
 def write_ppm(rgb: np.ndarray, path: str, samples_per_pixel: int = 1) -> None:
     """P3 writer of the reference (write_color, math.rs:119-132; main.rs:472, 591-596):
     height x width x 3, row 0 = bottom. An f64 array takes rt_write_ppm_f64 — the reference's
@@ -771,6 +838,60 @@ class Renderer:
         p = DenoiseParams(int(width), int(height), int(out_format), 1, int(radius), int(patch), float(k), stream)
         _check(self.lib.rt_denoise(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr), ctypes.c_void_p(stderr_ptr),
                                    ctypes.c_void_p(out_ptr)), "rt_denoise")
+
+    def denoise_guided(self, mean, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS, radius: int = 10,
+                       patch: int = 3, k: float = 0.45) -> np.ndarray:
+        """rt_denoise_guided on host arrays (synchronous): denoise with the feature buffers of
+        render_features in its weights; None leaves a guide out; sigmas = (albedo, normal, depth)."""
+        p, m, s = _denoise_args(mean, se, radius, patch, k)
+        g, keep = _guide_args(m.shape[:2], albedo, normal, depth, sigmas)
+        out = np.empty_like(m)
+        _check(self.lib.rt_denoise_guided(self.h, ctypes.byref(p), m.ctypes.data, s.ctypes.data, ctypes.byref(g),
+                                          out.ctypes.data), "rt_denoise_guided")
+        del keep
+        return out
+
+    def denoise_guided_device(self, mean_ptr: int, stderr_ptr: int, out_ptr: int, width: int, height: int,
+                              albedo_ptr: int = 0, normal_ptr: int = 0, depth_ptr: int = 0, sigmas=GUIDE_SIGMAS,
+                              out_format: int = RT_OUT_F32, radius: int = 10, patch: int = 3, k: float = 0.45,
+                              stream: Optional[int] = None):
+        """Enqueues rt_denoise_guided over device buffers on `stream`: as denoise_device, with the
+        guide frames (f64; 0 leaves one out) render_features_device wrote."""
+        p = DenoiseParams(int(width), int(height), int(out_format), 1, int(radius), int(patch), float(k), stream)
+        sa, sn, sz = (float(v) for v in sigmas)
+        g = DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+        _check(self.lib.rt_denoise_guided(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr),
+                                          ctypes.c_void_p(stderr_ptr), ctypes.byref(g), ctypes.c_void_p(out_ptr)),
+               "rt_denoise_guided")
+
+    def render_features(self, camera: Camera, params: RenderParams, albedo: bool = True, normal: bool = True,
+                        depth: bool = True):
+        """rt_render_features: the first hit's (albedo height x width x 3, normal height x width x 3,
+        depth height x width), f64 means over params.spp samples of rt_render's primary rays; a
+        buffer switched off comes back as None."""
+        W, H = params.width, params.height
+        a = np.empty((H, W, 3), dtype=np.float64) if albedo else None
+        n = np.empty((H, W, 3), dtype=np.float64) if normal else None
+        d = np.empty((H, W), dtype=np.float64) if depth else None
+        params.out_on_device = 0
+        out = FeaturesOut(*(x.ctypes.data if x is not None else None for x in (a, n, d)))
+        _check(self.lib.rt_render_features(self.h, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(out)),
+               "rt_render_features")
+        return a, n, d
+
+    def render_features_device(self, camera: Camera, params: RenderParams, albedo_ptr: int = 0, normal_ptr: int = 0,
+                               depth_ptr: int = 0, stream: Optional[int] = None):
+        """Enqueues rt_render_features into device buffers (f64; 0 leaves one out) on `stream`."""
+        params.out_on_device = 1
+        params.stream = stream
+        out = FeaturesOut(albedo_ptr or None, normal_ptr or None, depth_ptr or None)
+        _check(self.lib.rt_render_features(self.h, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(out)),
+               "rt_render_features")
+
+    def features_stats(self) -> FeaturesStats:
+        s = FeaturesStats()
+        _check(self.lib.rt_features_last_stats(self.h, ctypes.byref(s)), "rt_features_last_stats")
+        return s
 
     def denoise_stats(self) -> DenoiseStats:
         s = DenoiseStats()

@@ -18,9 +18,17 @@ Error: RMSE of sqrt(clamp(mean, 0, 0.999)) (the output's gamma) against a unifor
 error map of its own adaptive call (the uniform frame: of an adaptive call at threshold 0, which
 renders the same frame); reported are rmse_denoised beside rmse, the filter kernel's HIP-event time
 and the wall time of the host-pointer call (copies included). Without it the output is unchanged.
+--features SPP: every repetition also times the first-hit feature pass (rt_render_features at SPP
+samples per pixel): its HIP-event time (trace_features + its reduction) and the host-pointer call's
+wall time. --guided SA SN SZ (with --denoise): after the plain filter the same frame goes through
+rt_denoise_guided with the feature buffers (at --features SPP, default 16) and these sigmas (albedo,
+normal, depth); rmse_guided is reported beside rmse and rmse_denoised, against the same reference,
+with the guided kernel's time. --parent-denoise: the parent library filters its uniform frame too
+(the plain filter's time on the commit before).
 
 usage: python scripts/adaptive_bench.py --config C2 --thresholds 0.02 0.01 0.005 \
            [--parent lib/librtiow_parent.so] [--min-spp 64 --step-spp 64] [--denoise 10 3 0.45]
+           [--features 16] [--guided 0.1 0.2 0.1] [--parent-denoise]
            [--out adaptive_c2.json]
 """
 import argparse
@@ -58,7 +66,19 @@ if a["ref"]:
     ref = gamma(np.load(a["ref"]))
 res = {{}}
 dn = a.get("denoise")
+ft, gd = a.get("features"), a.get("guided")
 uniform_se = []
+guides = []
+def features(d):
+    pf = rt.Renderer.params(W, H, ft, a["depth"], bg, 1, out_format=rt.RT_OUT_F64)
+    t0 = time.perf_counter()
+    g = r.render_features(cam, pf)
+    d["features_wall_ms"] = (time.perf_counter() - t0) * 1e3
+    st = r.features_stats()
+    d.update(features_ms=st.kernel_ms + st.reduce_ms, features_kernel_ms=st.kernel_ms, features_reduce_ms=st.reduce_ms,
+             features_spp=ft)
+    if not guides:
+        guides.append(g)
 def denoised(mode, img, se, d):
     if mode == "uniform":
         if not uniform_se:   # the same frame's error map: an adaptive call that never stops early
@@ -70,7 +90,13 @@ def denoised(mode, img, se, d):
     d["denoise_wall_ms"] = (time.perf_counter() - t0) * 1e3
     st = r.denoise_stats()
     d.update(denoise_kernel_ms=st.kernel_ms, denoise_lds_bytes=st.lds_bytes)
-    return out
+    if gd:
+        t0 = time.perf_counter()
+        out_g = r.denoise_guided(img, se, *guides[0], gd, int(dn[0]), int(dn[1]), float(dn[2]))
+        d["guided_wall_ms"] = (time.perf_counter() - t0) * 1e3
+        d["guided_kernel_ms"] = r.denoise_stats().kernel_ms
+        return out, out_g
+    return out, None
 def run(mode):
     p = rt.Renderer.params(W, H, spp, a["depth"], bg, 1, out_format=rt.RT_OUT_F32)
     t0 = time.perf_counter()
@@ -90,19 +116,26 @@ def run(mode):
     return img, se, d
 for mode in a["modes"]:
     img, se, d = run(mode)                     # warm-up: code objects, buffers
+    if ft:
+        features(d)
     if dn:
         denoised(mode, img, se, d)
 for _ in range(a["reps"]):
     for mode in a["modes"]:
         img, se, d = run(mode)
-        out = denoised(mode, img, se, d) if dn else None
+        if ft:
+            features(d)
+        out, out_g = denoised(mode, img, se, d) if dn else (None, None)
         e = res.setdefault(mode, dict(runs=[]))
         e["runs"].append(d)
         if ref is not None and "rmse" not in e:
             e["rmse"] = float(np.sqrt(np.mean((gamma(img) - ref) ** 2)))
             if dn:
                 e["rmse_denoised"] = float(np.sqrt(np.mean((gamma(out) - ref) ** 2)))
+            if out_g is not None:
+                e["rmse_guided"] = float(np.sqrt(np.mean((gamma(out_g) - ref) ** 2)))
 print("RESULT", json.dumps(res))
+print("BUILD", rt.build_info())
 """
 
 
@@ -124,21 +157,32 @@ def main():
     ap.add_argument("--ref-mult", type=int, default=4, help="the error reference: uniform at this many x spp (0: none)")
     ap.add_argument("--denoise", type=float, nargs=3, default=None, metavar=("R", "F", "K"),
                     help="also filter every frame with rt_denoise: radius, patch, k")
+    ap.add_argument("--features", type=int, default=None, metavar="SPP",
+                    help="also time rt_render_features at SPP samples per pixel")
+    ap.add_argument("--guided", type=float, nargs=3, default=None, metavar=("SA", "SN", "SZ"),
+                    help="with --denoise: also filter with rt_denoise_guided (sigmas of albedo, normal, depth)")
+    ap.add_argument("--parent-denoise", action="store_true", help="the parent library runs the plain filter too")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.guided and not a.denoise:
+        ap.error("--guided needs --denoise R F K")
+    if a.guided and not a.features:
+        a.features = 16
     cfg = CONFIGS[a.config]
     tmp = tempfile.TemporaryDirectory()   # the error reference: rendered by the first child, read by the others
     ref = os.path.join(tmp.name, f"adaptive_ref_{a.config}_x{a.ref_mult}.npy") if a.ref_mult > 0 else None
     jobs = [("new", a.lib, ["uniform"] + [repr(t) for t in a.thresholds])]
     if a.parent:
         jobs.insert(0, ("parent", a.parent, ["uniform"]))
-    runs = {}
+    runs, builds = {}, {}
     for _ in range(a.rounds):
         for name, lib, modes in jobs:
             args = dict(cfg, modes=modes, reps=a.reps, min_spp=a.min_spp, step_spp=a.step_spp, ref=ref,
                         ref_mult=a.ref_mult)
-            if a.denoise and name == "new":
+            if a.denoise and (name == "new" or a.parent_denoise):
                 args["denoise"] = a.denoise
+            if name == "new":
+                args.update(features=a.features, guided=a.guided)
             env = dict(os.environ, RT_LIB_PATH=os.path.abspath(os.path.join(REPO, lib)))
             out = subprocess.run([sys.executable, "-c", CHILD.format(repo=REPO, args=json.dumps(args))], env=env,
                                  capture_output=True, text=True, timeout=900)
@@ -146,8 +190,12 @@ def main():
                 print(f"{name}: child failed ({out.returncode})\n{out.stderr[-2000:]}")
                 sys.exit(out.returncode if out.returncode > 0 else 1)
             d = json.loads([x for x in out.stdout.splitlines() if x.startswith("RESULT ")][-1][7:])
+            if name not in builds:   # rt_build_info of each library, once
+                builds[name] = [x for x in out.stdout.splitlines() if x.startswith("BUILD ")][-1][6:]
+                print(f"  {name}: rt_build_info {builds[name]}", flush=True)
             for mode, e in d.items():
-                k = runs.setdefault(f"{name}:{mode}", dict(runs=[], rmse=e.get("rmse"), rmse_denoised=e.get("rmse_denoised")))
+                k = runs.setdefault(f"{name}:{mode}", dict(runs=[], rmse=e.get("rmse"), rmse_denoised=e.get("rmse_denoised"),
+                                                           rmse_guided=e.get("rmse_guided")))
                 k["runs"] += e["runs"]
                 print(f"  {name}:{mode}: wall {['%.2f' % x['wall_ms'] for x in e['runs']]}", flush=True)
     uniform_px = cfg["width"] * cfg["height"] * cfg["spp"]
@@ -165,8 +213,18 @@ def main():
             s["tile_error_pct_5_25_50_75_95_100"] = rs[0]["tile_error_pct"]
         if "denoise_kernel_ms" in rs[0]:
             s.update(rmse_denoised=e["rmse_denoised"], denoise_kernel_ms=median([x["denoise_kernel_ms"] for x in rs]),
+                     denoise_kernel_ms_min=min(x["denoise_kernel_ms"] for x in rs),
+                     denoise_kernel_ms_max=max(x["denoise_kernel_ms"] for x in rs),
                      denoise_wall_ms=median([x["denoise_wall_ms"] for x in rs]), denoise_lds_bytes=rs[0]["denoise_lds_bytes"],
                      denoise_kernel_over_wall=median([x["denoise_kernel_ms"] for x in rs]) / median(wall))
+        if "features_ms" in rs[0]:
+            s.update(features_spp=rs[0]["features_spp"], features_ms=median([x["features_ms"] for x in rs]),
+                     features_kernel_ms=median([x["features_kernel_ms"] for x in rs]),
+                     features_reduce_ms=median([x["features_reduce_ms"] for x in rs]),
+                     features_wall_ms=median([x["features_wall_ms"] for x in rs]))
+        if "guided_kernel_ms" in rs[0]:
+            s.update(rmse_guided=e["rmse_guided"], guided_kernel_ms=median([x["guided_kernel_ms"] for x in rs]),
+                     guided_wall_ms=median([x["guided_wall_ms"] for x in rs]), guided_sigmas=a.guided)
         for k in ("passes", "classify_ms", "mean_tile_spp", "tiles_at_max", "tiles_at_min", "tiles", "schedule", "n_batches",
                   "max_pass_batches"):
             if k in rs[0]:
@@ -177,6 +235,10 @@ def main():
         doc = dict(config=a.config, params=cfg, min_spp=a.min_spp, step_spp=a.step_spp, base_wall_ms=base, results=summary)
         if a.denoise:
             doc["denoise"] = a.denoise
+        if a.features:
+            doc["features_spp"] = a.features
+        if a.guided:
+            doc["guided"] = a.guided
         json.dump(doc, open(a.out, "w"), indent=1)
 
 
