@@ -591,7 +591,7 @@ int rt_ctx_upload_soa(rt_ctx* c, const rt_scene_soa* s)
     S.stack_entries = L.stack_entries;
     S.n_tlas_nodes = L.n_tlas_nodes;
     S.n_blas_bfs = L.n_blas_bfs;
-    S.n_lds_nodes = S.n_lds_blas = 0;   // a launch decides what it stages in LDS
+    S.n_lds_nodes = S.n_lds_blas = S.seed_stage_bytes = 0;   // a launch decides what it stages in LDS
     S.has_lights = L.has_lights;
     S.has_spheres = L.has_spheres;
     c->scene = rtp::scene_facts(L, *s);
@@ -870,6 +870,7 @@ static int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p,
     S.n_lds_materials = pl.n_lds_materials;
     S.n_lds_textures = pl.n_lds_textures;
     S.n_lds_blas = pl.n_lds_blas;
+    S.seed_stage_bytes = (int32_t)pl.seed_stage_bytes;
     K.block_chunks = pl.block_chunks;
     K.block_samples = pl.block_samples;
     K.ring_waves = pl.ring_waves;

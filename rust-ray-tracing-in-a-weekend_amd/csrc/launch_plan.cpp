@@ -243,6 +243,25 @@ Plan plan(const SceneFacts& scene, const DeviceFacts& dev, const Options& opt, c
     // k & 1 on stream tstream[k & 1] while the caller's stream reduces batch k - 1, so the
     // next trace fills the CUs its predecessor's last waves leave (no tail per batch).
     pl.per_sample = pl.schedule == RT_SCHED_POOL && !pl.ring;
+    // Wave-wide sample starts (launch_shapes.hpp, RT_STAGE_SEEDS): the f64 spheres variant's
+    // 16-bit-stack per-sample pool kernels, buffer and ring forms, keep one 32 B slot per lane in LDS
+    // after the stack — while that costs the variant no resident workgroup (6 waves per SIMD: 24
+    // per CU; each allocation rounded to the 1 KB granule as for the staged BLAS above). The random
+    // scene: 22.2 KB of node records + 19.5 KB of stack + 24 KB = 66 KB, two 768-thread workgroups in
+    // 160 KB as before; a scene whose stack leaves no room keeps the per-lane sample starts.
+    const bool s16 = variant == rtk::FEAT_SET_SPHERES &&
+                     rtk::stack16_launch(pl.slab32, pl.lds_stack, pl.n_lds_nodes, scene.n_tlas_nodes, scene.stack16_ok != 0);
+    if (RT_STAGE_SEEDS && s16 && !pl.f32 && pl.schedule == RT_SCHED_POOL) {
+        const int bt = rtk::block_threads_of(variant, false, true);
+        const size_t granule = 1024, stage = rtk::seed_stage_bytes_of(bt);
+        // (the slots start on a 32 B boundary: trace_device.hpp, lds_seeds_offset)
+        const size_t base = ((size_t)pl.n_lds_nodes * 80 + (size_t)scene.stack_entries * (size_t)bt * 2 + 31) / 32 * 32;
+        auto resident = [&](size_t bytes) {
+            const size_t alloc = (std::max<size_t>(bytes, 1) + granule - 1) / granule * granule;
+            return alloc > dev.lds_per_block ? (size_t)0 : std::min<size_t>(std::max(1, 24 / (bt / 64)), dev.lds_per_cu / alloc);
+        };
+        if (resident(base + stage) > 0 && resident(base + stage) == resident(base)) pl.seed_stage_bytes = stage;
+    }
     const size_t unit = pl.per_sample ? sample_bytes : px_bytes;
     long long fit = (long long)std::max<size_t>(1, out_cap / unit);
     pl.batch = std::min<long long>(total, pl.per_sample ? fit : fit * chunk);

@@ -84,6 +84,9 @@ struct Plan {
     int schedule = 0;           // RT_SCHED_*, AUTO resolved
     // staged in LDS (SceneDev's fields of these names)
     int n_lds_nodes = 0, n_lds_materials = 0, n_lds_textures = 0, n_lds_blas = 0;
+    // LDS bytes per workgroup of the wave-wide sample starts (SceneDev.seed_stage_bytes; launch_shapes.hpp
+    // RT_STAGE_SEEDS): 32 B x 64 x the workgroup's waves on the kernels that stage, 0 on all others
+    size_t seed_stage_bytes = 0;
     // work blocks, the in-kernel reduction
     int block_chunks = 0, block_samples = 0;
     bool ring = false;

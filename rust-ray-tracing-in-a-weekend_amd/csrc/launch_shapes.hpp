@@ -86,6 +86,23 @@ constexpr int kRingSampleBits = 20;            // ring: samples below 2^20, the 
 constexpr uint32_t kRingSampleMask = (1u << kRingSampleBits) - 1;
 static_assert(kPoolRing * kRingSlot <= (1u << (32 - kRingSampleBits)), "ring record index bits");
 
+// Wave-wide sample starts (trace_pool's staged instantiations): units of a work
+// block are dealt sample-major, so the 64 samples a wave starts next are always one sample of its
+// tile's 64 pixels. The wave seeds and jitters that whole row at once — lane p pixel p — into a
+// staging area of its own in LDS (kSeedSlotBytes per pixel: the path stream after the jitter
+// draws, then u and v), and a lane that takes a unit reads its slot, instead of the ~22 lanes
+// that start a sample in a bounce-loop iteration running the sequence under their exec mask.
+// The f64 spheres variant's 16-bit-stack per-sample pool kernels only (buffer and ring forms);
+// the host's plan decides per launch (rtp::Plan.seed_stage_bytes). 0: compiled out (A/B builds).
+// C2 1200x800x500 against the parent commit's library, 18 renders each: 70.39 -> 68.14 ms, every
+// frame identical; the count variant's "seeding + jitter" share 0.067 -> 0.019 of wave time, the
+// refill's 0.140 -> 0.166 (profiles/staged_seeds_ab_c2.log, staged_seeds_phases_c2.log).
+#ifndef RT_STAGE_SEEDS
+#define RT_STAGE_SEEDS 1
+#endif
+constexpr size_t kSeedSlotBytes = 32;
+RT_LS_HD constexpr size_t seed_stage_bytes_of(int block_threads) { return kSeedSlotBytes * (size_t)block_threads; }
+
 // the per-sample buffer's records per sample: whole 8x8 tiles (trace_kernel.hpp, tiled_record)
 RT_LS_HD inline size_t tiled_pixels(int width, int n_rows)
 {

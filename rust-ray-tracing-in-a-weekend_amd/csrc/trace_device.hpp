@@ -161,6 +161,14 @@ struct Cfg {
     // reduced configurations of nested code (CfgDrop), which share its LDS stack
     static constexpr int BT = block_threads_of(F_, F32_, RT_STACK16 && LDS_ && NALL_ && S32_);
     using Real = typename std::conditional<F32_, float, double>::type;
+    static constexpr bool STAGE = false;   // (CfgStage below)
+};
+// The configuration of trace_pool's staged instantiations (launch_shapes.hpp, RT_STAGE_SEEDS): the
+// wave seeds and jitters a whole row of samples at once. A configuration of its own rather than a
+// template parameter of the kernel, so every other instantiation keeps its symbol and its code.
+template <class C>
+struct CfgStage : C {
+    static constexpr bool STAGE = true;
 };
 
 // The configuration of code reached only through an instance or a medium boundary: the
@@ -854,6 +862,10 @@ __host__ __device__ constexpr LdsLayout lds_layout(int n_nodes, int node_bytes, 
     const size_t shade = stack + (size_t)stack_entries * (size_t)lanes * (size_t)entry_bytes;
     return LdsLayout{blas, stack, shade, shade + (size_t)n_materials * 64 + (size_t)n_textures * 96};
 }
+// The staged sample starts (RT_STAGE_SEEDS) follow that layout on a boundary of their slots' size
+// (kSeedSlotBytes): their byte offset from the layout's total. (A function of its own: the layout
+// function above is inlined by cost, and the kernels that do not stage keep their code.)
+__host__ __device__ constexpr size_t lds_seeds_offset(size_t layout_total) { return (layout_total + 31) / 32 * 32; }
 // the variants that stage BLAS nodes (SceneDev.n_lds_blas; the host sets it only for them)
 #ifndef RT_STAGE_BLAS
 #define RT_STAGE_BLAS 1
@@ -2141,6 +2153,27 @@ constexpr bool RingSgpr() { return C::F == FEAT_SET_SPHERES; }
 template <class C>
 constexpr bool DealCfg() { return RT_DEAL != 0 && deal_variant(C::F) && !C::COUNT; }
 
+// Wave-wide sample starts (launch_shapes.hpp, RT_STAGE_SEEDS; the per-sample pool's CfgStage
+// instantiations). A slot is what a lane needs to start its sample in the `cam_wait` state: the
+// path stream after the two jitter draws, and the jitter. Slot j of the workgroup's area belongs
+// to lane j % 64 of wave j / 64, so the writer's index is threadIdx.x.
+struct alignas(32) SeedSlot {
+    rt_pstream st;
+    double u, v;
+};
+static_assert(sizeof(SeedSlot) == kSeedSlotBytes, "a staged sample start is one slot");
+template <class C, bool ITEMS>
+constexpr bool StagedPool()   // trace_pool<C, ITEMS, ...> stages: the f64 spheres variant's 16-bit-stack per-sample pool kernels
+{
+    static_assert(!C::STAGE || (Stack16Cfg<C>() && RingSgpr<C>() && !C::F32), "staged sample starts: the f64 spheres variant's 16-bit-stack kernels");
+    return C::STAGE && !ITEMS;
+}
+template <class C>
+__device__ __forceinline__ SeedSlot* seed_slots(const SceneDev& S)   // derived where used, like lds_stack_offset: nothing of it lives through the walk
+{
+    return reinterpret_cast<SeedSlot*>(reinterpret_cast<char*>(rt_lds) + lds_seeds_offset(lds_layout_of<C>(S).total));
+}
+
 __device__ __forceinline__ void ring_reduce(const KParams& P, const double* __restrict__ rec,
                                             double* __restrict__ partial, unsigned blk, unsigned n_tiles, unsigned group,
                                             size_t n_px, int lane)
@@ -2241,6 +2274,13 @@ __global__ void __launch_bounds__(BlockThreads<C>(), min_waves<C>()) trace_pool(
     // as else-branches the spheres variant's kernel compiled to other code, 1.4 % slower on C2)
     int ringv = 0;                       // !RingSgpr: lane q slot q's block, kRingCur, kRingOcc
     unsigned occ = 0, cur_slot = 0;      // RingSgpr (the other form: read from ringv where used)
+    // Staged sample starts (StagedPool): when units are taken from the start of a sample row of the
+    // block, the wave first seeds and jitters the whole row — lane p the tile's pixel p — into its
+    // LDS slots; a lane that takes a unit reads its slot and is then in the `cam_wait` state (the
+    // stream past the jitter draws, u and v in r.dx / r.dy), so ray generation holds no seeding
+    // code. Everything is derived from blk_next, nvalid, s0, tx0 and tk0: no state of its own, and
+    // no local of its own here either (a constant declared at this point changed the ring kernels'
+    // register allocation in every variant).
     for (;;) {
         if constexpr (ring && !RingSgpr<C>()) {   // (final variant) the same, the state in ringv's lanes
             unsigned occv = (unsigned)__builtin_amdgcn_readlane(ringv, kRingOcc);
@@ -2369,6 +2409,80 @@ __global__ void __launch_bounds__(BlockThreads<C>(), min_waves<C>()) trace_pool(
                 blk_next = 0;
             }
             const unsigned rank = lanes_below(need);
+            if constexpr (StagedPool<C, ITEMS>()) {
+                // the block's sample row units are taken from, and the next pixel of it (wave-uniform)
+                unsigned row, col;
+                if (nvalid == 64u) {
+                    row = blk_next >> 6;
+                    col = blk_next & 63u;
+                } else {
+                    row = blk_next / nvalid;
+                    col = blk_next - row * nvalid;
+                }
+                if (col == 0) {   // a new row: every pixel's sample start at once, one issue of the sequence per 64 samples
+                    uint64_t t_stage = 0;
+                    if (C::COUNT) t_stage = __builtin_amdgcn_s_memtime();
+                    if ((unsigned)lane < nvalid) {
+                        int px, pk;
+                        if (nvalid == 64u) {
+                            px = tx0 + (lane & 7);
+                            pk = tk0 + (lane >> 3);
+                        } else {
+                            px = tx0 + (int)((unsigned)lane % (unsigned)vw);
+                            pk = tk0 + (int)((unsigned)lane / (unsigned)vw);
+                        }
+                        int ix, y;
+                        image_xy(P, px, pk, ix, y);
+                        SeedSlot sl;
+                        ds_start(sl.st, P.seed, (uint32_t)y * (uint32_t)P.img_width + (uint32_t)ix, (uint32_t)(s0 + (int)row));
+                        camera_begin(P, ix, y, sl.st, sl.u, sl.v);
+                        seed_slots<C>(S)[threadIdx.x] = sl;
+                    }
+                    // Other lanes of this wave read the slots below, and in later passes: a wave's LDS
+                    // accesses complete in program order, so keeping the compiler from moving them
+                    // across this point orders them; no workgroup barrier (the area is the wave's own).
+                    // The previous row was taken to its last unit before this one was written.
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    if (C::COUNT && lane == 0) {   // staging ran inside the refill: its time is seeding + jitter
+                        const uint64_t dt = __builtin_amdgcn_s_memtime() - t_stage;   // (the counters are summed over lanes,
+                        cnt.t_seed += dt;                                           // mod 2^64: one lane moves the interval)
+                        cnt.t_refill -= dt;
+                        cnt.cam_steps++;
+                    }
+                }
+                // a pass never crosses a row (the loop's next pass stages and takes from the next one)
+                const unsigned take = min(min((unsigned)__popcll(need), nvalid - col), blk_units - blk_next);
+                if (!active && rank < take) {
+                    const unsigned p = col + rank;
+                    if (nvalid == 64u) {
+                        x = tx0 + (int)(p & 7u);
+                        k = tk0 + (int)(p >> 3);
+                    } else {
+                        x = tx0 + (int)(p % (unsigned)vw);
+                        k = tk0 + (int)(p / (unsigned)vw);
+                    }
+                    s = s0 + (int)row;
+                    if (ring) s |= (int)((cur_slot * kRingSlot + row * 64u + (unsigned)((k & 7) * 8 + (x & 7))) << kRingSampleBits);
+                    const SeedSlot sl = seed_slots<C>(S)[(threadIdx.x & ~63u) + p];
+                    st = sl.st;
+                    r.dx = sl.u;
+                    r.dy = sl.v;
+                    Tr = Tg = Tb = (R)1;
+                    cr = cg = cb = 0.0;
+                    depth = P.max_depth;
+                    if (C::COUNT) {
+                        cnt.cam_lanes++;
+                        t_sample = __builtin_amdgcn_s_memtime();
+                    }
+                    active = true;
+                    new_sample = true;
+                }
+                blk_next += take;
+                need = __ballot(!active);
+                continue;
+            }
             const unsigned take = min((unsigned)__popcll(need), blk_units - blk_next);
             if (!active && rank < take) {
                 const unsigned u = blk_next + rank;
@@ -2431,7 +2545,12 @@ __global__ void __launch_bounds__(BlockThreads<C>(), min_waves<C>()) trace_pool(
             R u = 0, v = 0;
             bool tries = false;
             if (new_sample) {
-                if (TryLeft<C>() && cam_wait) {   // camera_begin ran: the jitter waits in r.dx / r.dy
+                if constexpr (StagedPool<C, ITEMS>()) {
+                    // the refill left the lane as camera_begin leaves it: every new sample's jitter waits
+                    // in r.dx / r.dy (cam_wait is implied; the spheres variant reads no key.pixel / key.sample)
+                    u = r.dx;
+                    v = r.dy;
+                } else if (TryLeft<C>() && cam_wait) {   // camera_begin ran: the jitter waits in r.dx / r.dy
                     u = r.dx;
                     v = r.dy;
                     cam_wait = false;
@@ -2649,14 +2768,27 @@ static void launch_one(const Launch& L, hipStream_t stream, bool nall)
     const bool stage = F != FEAT_SET_SPHERES;                   // StageShade
     const bool blas = RT_STAGE_BLAS && (F & FEAT_INST_BLAS) != 0;   // StageBlas
     const int bt = block_threads_of(F, F32, RT_STACK16 && LDS && nall && S32), wpb = bt / 64;   // BlockThreads
-    const size_t lds = lds_layout(S.n_lds_nodes, node_bytes, blas ? S.n_lds_blas : 0, LDS ? S.stack_entries : 0,
-                                  s16 ? 2 : 4, stage ? S.n_lds_materials : 0, stage ? S.n_lds_textures : 0, bt).total;
+    // wave-wide sample starts (RT_STAGE_SEEDS): the plan's bytes for this launch pick the per-sample
+    // pool's staged instantiation, which exists for the f64 16-bit-stack spheres kernels only
+    constexpr bool can_stage = RT_STAGE_SEEDS && RT_STACK16 && F == FEAT_SET_SPHERES && S32 && LDS && !F32;
+    const int seed_bytes = can_stage && nall && L.pool == 1 && S.seed_stage_bytes == (int)seed_stage_bytes_of(bt)
+                               ? S.seed_stage_bytes : 0;
+    const size_t lds_rest = lds_layout(S.n_lds_nodes, node_bytes, blas ? S.n_lds_blas : 0, LDS ? S.stack_entries : 0,
+                                       s16 ? 2 : 4, stage ? S.n_lds_materials : 0, stage ? S.n_lds_textures : 0, bt).total;
+    const size_t lds = seed_bytes ? lds_seeds_offset(lds_rest) + (size_t)seed_bytes : lds_rest;
     if (L.pool) {
         auto go = [&](auto kernel) {
             unsigned nb = std::min<unsigned long long>(resident_blocks(L, kernel, lds, bt), (L.n_blocks + wpb - 1) / wpb);
             if (L.max_waves) nb = std::max(1u, std::min(nb, L.max_waves / (unsigned)wpb));
             hipLaunchKernelGGL(kernel, dim3(nb), dim3(bt), lds, stream, S, L.P, L.out, L.counters, L.work);
         };
+        if constexpr (can_stage) {
+            if (seed_bytes) {
+                if (L.max_waves) go(trace_pool<CfgStage<Cfg<F, S32, LDS, true, COUNT, F32>>, false, true>);
+                else go(trace_pool<CfgStage<Cfg<F, S32, LDS, true, COUNT, F32>>, false>);
+                return;
+            }
+        }
         if (L.pool == 2) {
             if (nall) go(trace_pool<Cfg<F, S32, LDS, true, COUNT, F32>, true>);
             else go(trace_pool<Cfg<F, S32, LDS, false, COUNT, F32>, true>);
@@ -2706,6 +2838,12 @@ static void launch_f(const Launch& L, int slab32, int lds, hipStream_t stream)
                                  (const void*)trace_chunks<Cfg<F, true, true, true, COUNT, false>>};
             for (const void* k : ks)
                 if (hipFuncGetAttributes(&a, k) != hipSuccess || a.sharedSizeBytes != 0) static_lds = 1;
+            if constexpr (RT_STAGE_SEEDS != 0 && RT_STACK16 != 0 && S16F) {   // the staged per-sample pool kernels (launch_one)
+                const void* kst[2] = {(const void*)trace_pool<CfgStage<Cfg<F, true, true, true, COUNT, false>>, false>,
+                                      (const void*)trace_pool<CfgStage<Cfg<F, true, true, true, COUNT, false>>, false, true>};
+                for (const void* k : kst)
+                    if (hipFuncGetAttributes(&a, k) != hipSuccess || a.sharedSizeBytes != 0) static_lds = 1;
+            }
         }
         if (static_lds) nall = false;
     }

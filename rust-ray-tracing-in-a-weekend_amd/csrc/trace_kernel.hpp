@@ -49,7 +49,11 @@ struct SceneDev {
     // nodes[n_tlas_nodes, n_tlas_nodes + n_blas_bfs) (scene_lower.cpp), and a launch stages the first
     // n_lds_blas of them (its LDS budget): the nested walk's top levels then read LDS
     int32_t n_blas_bfs, n_lds_blas;
-    int32_t pad0;           // (unused: keeps the kernel-argument layout the kernels were timed with)
+    // LDS bytes per workgroup of the wave-wide sample starts, after the rest of the layout (the host's
+    // plan, rtp::Plan.seed_stage_bytes); > 0 launches trace_pool's staged instantiation, 0 (every
+    // other kernel, or no room) the per-lane one. (In the slot of a former padding word: the
+    // kernel-argument layout is the one the kernels were timed with.)
+    int32_t seed_stage_bytes;
 };
 
 struct KParams {

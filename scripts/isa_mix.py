@@ -102,8 +102,13 @@ def kernel_asm(variant, items, slab32=1, nall=1, ring=False):
                    capture_output=True)
     lines = open(out).read().splitlines()
     f = FEAT[variant]
-    name = re.compile(r"^(_ZN3rtk10trace_poolINS_3CfgILj%dELb%dELb1ELb%dELb0ELb0EEELb%dELb%dEEE\S*):"
-                      % (f, slab32, nall, int(items), int(ring)))
+    cfg = "3CfgILj%dELb%dELb1ELb%dELb0ELb0EEE" % (f, slab32, nall)
+    name = re.compile(r"^(_ZN3rtk10trace_poolINS_%sLb%dELb%dEEE\S*):" % (cfg, int(items), int(ring)))
+    # the per-sample pool's staged instantiation (CfgStage<Cfg<...>>, RT_STAGE_SEEDS) is the one a
+    # launch runs where the unit holds it (the f64 spheres variant's 16-bit-stack kernels)
+    staged = re.compile(r"^(_ZN3rtk10trace_poolINS_8CfgStageINS_%sEELb%dELb%dEEE\S*):" % (cfg, int(items), int(ring)))
+    if any(staged.match(l) for l in lines):
+        name = staged
     start = next(i for i, l in enumerate(lines) if name.match(l))
     end = next(i for i in range(start + 1, len(lines)) if lines[i].strip().startswith(".size"))
     return name.match(lines[start]).group(1), lines[start:end]

@@ -53,7 +53,9 @@ def kernels(path: str) -> dict:
             if s.startswith(".Lfunc_end"):
                 cur = None
             continue
-        out[cur].append(s)
+        # block labels carry the function's index in its translation unit (.LBB<fn>_<block>): a kernel
+        # added to the unit renumbers every later one's labels and nothing else
+        out[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", s))
     return out
 
 
