@@ -33,6 +33,8 @@
  *   rt_render_features        (new) the first hit of the same primary rays (camera.rs:58-66) as
  *                             albedo, normal and depth buffers; the reference writes none
  *   rt_denoise_guided         (new) rt_denoise with those buffers in its weights
+ *   rt_denoise_atrous         (new) a second post-filter: an edge-stopping a-trous wavelet over the
+ *                             same inputs, which also hands back the noise left in its result
  *
  * Threading: a context is bound to one device and is used by one host thread at
  * a time. Worlds are plain host objects.
@@ -625,6 +627,75 @@ int rt_denoise_guided(rt_ctx* ctx, const rt_denoise_params* p, const void* mean,
 /* The same filter on the host, no device needed (on_device and stream are ignored). */
 int rt_denoise_guided_host(const rt_denoise_params* p, const void* mean, const double* stderr_map,
                            const rt_denoise_guides* g, void* out);
+
+/* ---- variance-guided a-trous wavelet denoiser (additive to ABI v6: new symbols only) ------------
+ * A second filter beside rt_denoise, for noise broader than NL-means' 21 x 21 window or a frame
+ * budget without milliseconds for a filter: the edge-stopping a-trous wavelet of Dammertz et al.
+ * 2010 with the variance-scaled luminance stop of SVGF's spatial filter (Schied et al. 2017). L
+ * levels of 25 taps at steps 1, 2, 4, ... cover a (4 (2^L - 1) + 1)^2 footprint (125 x 125 at
+ * L = 5) with 25 L taps per pixel. The variance is carried through every level and handed back.
+ *
+ * Inputs: M, height x width x 3 mean radiance (f32 or f64, row 0 = bottom); se, height x width f64
+ * (rt_adaptive_out.stderr_map); optional guides g (rt_denoise_guides with rt_denoise_guided's
+ * meaning; NULL or all three frames NULL: no feature term); levels L in 1..6; sigma_l > 0 and
+ * finite; demodulate 0 or 1. All arithmetic is f64 with no contraction and no fast math; f32 input
+ * is widened first. Y(c) is the luminance of a colour c by rt_render_adaptive's expression.
+ * State, per pixel: a colour C (3 channels) and a variance V.
+ *   C_0 = M,  V_0 = se^2
+ * With demodulate = 1 (needs a non-NULL albedo guide A), per channel c:
+ *   A'_c(p) = A_c(p) if it is finite and > 0.01, 0.01 if it is finite and <= 0.01, 1 if it is not finite
+ *   C_0,c = M_c / A'_c,  V_0 = se^2 / (Y(A') Y(A'))
+ * A first-hit mean albedo demodulates a multi-bounce mean colour only approximately: the light a
+ * path gathers after its first hit is tinted by later surfaces, and the mean of products is not the
+ * product of means; C_0 is a smoother signal than M on a textured surface, not an irradiance.
+ * Level i = 0..L-1, step s = 2^i, everything read from state i:
+ *   Vbar(p) = the 3 x 3 binomial mean of V_i around p at distance 1 (not stepped), weights
+ *             (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4), over the neighbours inside the image whose V_i is
+ *             finite, divided by the sum of the weights taken, in raster order (dy outer, dx inner)
+ *   dl(p)   = sigma_l sqrt(max(0, Vbar(p))) + 1e-10
+ *   for the 25 taps q = p + s (dx, dy), dx, dy in -2..2, in raster order, with
+ *   h = (1/16, 1/4, 3/8, 1/4, 1/16) and h(dx, dy) = h[dy+2] h[dx+2]:
+ *     the centre tap has w = h(0, 0); a tap outside the image has no term; otherwise
+ *     e = |Y(C_i(p)) - Y(C_i(q))| / dl(p) + Phi(p, q), Phi exactly rt_denoise_guided's term read from
+ *         the guide frames at p and q (skipped without guides)
+ *     w = h(dx, dy) exp(-e) if e and V_i(q) are finite, else 0; terms with w = 0 are skipped, not
+ *         multiplied
+ *   C_{i+1}(p) = sum w C_i(q) / sum w
+ *   V_{i+1}(p) = sum w^2 V_i(q) / (sum w  sum w)
+ *   If Y(C_i(p)) or V_i(p) is not finite, the pixel keeps C_i(p) and V_i(p): a NaN pixel stays where
+ *   it is and does not spread.
+ * Output: out = C_L, multiplied by A' per channel when demodulated; where Y(M(p)) or se(p) is not
+ * finite, out(p) is M(p) bit for bit. The optional stderr_out (height x width f64) is sqrt(V_L),
+ * V_L first multiplied by Y(A') Y(A') when demodulated: the standard error left in out's luminance
+ * if the taps' errors were independent (they are not after the first level, so it is a lower
+ * estimate). out has M's format; an f32 out is the f64 result rounded once. Nothing depends on the
+ * device's tiling: the result repeats bit for bit, and the device and host filters differ only by
+ * their exp. */
+typedef struct rt_atrous_params {
+    int32_t width, height, format, on_device;  /* as rt_denoise_params */
+    int32_t levels, demodulate;
+    double sigma_l;
+    void* stream;        /* hipStream_t (NULL = the context's stream) */
+} rt_atrous_params;
+/* RT_ERR_INVALID as rt_denoise_guided returns it, and for out == mean, stderr_out == stderr_map,
+ * levels, sigma_l or demodulate out of range, demodulate without an albedo guide. Needs no uploaded
+ * scene. The guides, stderr_map and stderr_out are device pointers iff p->on_device; with it set the
+ * call is only enqueued, like rt_denoise. The states between the first and the last level live in
+ * scratch the context owns (none at L = 1, one frame of 32-byte records at L = 2, two above),
+ * allocated on first need and grown when a larger frame arrives: a call that grows it may wait for
+ * the stream, any other call with on_device set does no host-side wait. */
+int rt_denoise_atrous(rt_ctx* ctx, const rt_atrous_params* p, const void* mean, const double* stderr_map,
+                      const rt_denoise_guides* g, void* out, double* stderr_out /* may be NULL */);
+/* The same filter on the host, no device needed (on_device and stream are ignored). */
+int rt_denoise_atrous_host(const rt_atrous_params* p, const void* mean, const double* stderr_map,
+                           const rt_denoise_guides* g, void* out, double* stderr_out /* may be NULL */);
+
+typedef struct rt_atrous_stats {
+    double kernel_ms;       /* last rt_denoise_atrous: its kernels, summed over levels (HIP events; waits if only enqueued) */
+    int32_t levels;
+    int64_t scratch_bytes;  /* state scratch that call used: 0, 1 or 2 x (32 width height) */
+} rt_atrous_stats;
+int rt_atrous_last_stats(rt_ctx* ctx, rt_atrous_stats* out);
 
 /* ---- output ------------------------------------------------------------------------------ */
 /* P3 PPM byte for byte as the reference writes it (write_color, math.rs:119-132; main.rs:472,

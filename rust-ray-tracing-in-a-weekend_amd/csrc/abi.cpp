@@ -15,6 +15,7 @@
 
 #include "rt/rt_abi.h"
 #include "adaptive_criterion.hpp"
+#include "atrous.hpp"
 #include "ctx_internal.hpp"
 #include "deal_cache.hpp"
 #include "denoise.hpp"
@@ -92,6 +93,11 @@ struct rt_ctx {
     rt_features_stats fstats{};         // the last rt_render_features (rt_features_last_stats)
     hipEvent_t ev_ft[3] = {nullptr, nullptr, nullptr};   // before its trace launches, after them, after its reductions
     bool pending_ft = false;            // its times are still to be read from the events
+    rt_atrous_stats wstats{};           // the last rt_denoise_atrous (rt_atrous_last_stats)
+    hipEvent_t ev_at[2] = {nullptr, nullptr};   // around its level kernels
+    bool pending_at = false;            // its kernel_ms is still to be read from the events
+    rtk::AtrousRec* atrous_buf = nullptr;   // its state scratch between levels (grown on demand)
+    size_t atrous_cap = 0;              //   bytes
     // what a render's launch plan is made from (launch_plan.hpp): the uploaded scene, the device, the switches
     rtp::SceneFacts scene;
     rtp::DeviceFacts dev;
@@ -196,6 +202,7 @@ int rt_ctx_create(int device, rt_ctx** out)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev_dn[i]);
     for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev_ft[i]);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev_at[i]);
     if (e != hipSuccess) {
         rt_ctx_destroy(c);
         return hip_fail(e, "rt_ctx_create");
@@ -220,6 +227,7 @@ void rt_ctx_destroy(rt_ctx* c)
     (void)hipFree(c->params);
     (void)hipFree(c->work);
     (void)hipFree(c->acc_tmp);
+    (void)hipFree(c->atrous_buf);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->ev_done) (void)hipEventDestroy(c->ev_done);
@@ -233,6 +241,8 @@ void rt_ctx_destroy(rt_ctx* c)
     for (auto& e : c->ev_dn)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_ft)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->ev_at)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1619,6 +1629,108 @@ int rt_denoise_last_stats(rt_ctx* c, rt_denoise_stats* out)
         c->pending_dn = false;
     }
     *out = c->dstats;
+    return RT_OK;
+}
+
+// ---- variance-guided a-trous wavelet filter (rt_abi.h: the filter; atrous_kernel.hip; atrous_host.cpp)
+namespace {
+[[maybe_unused]] const bool g_atrous_sink_set = (rtk::atrous_error_sink = [](const char* msg) { g_last_error = msg; }, true);
+}  // namespace
+
+// The context's state scratch for a call that needs `bytes` of it (grown on demand).
+static int atrous_scratch(rt_ctx* c, hipStream_t stream, size_t bytes, rtk::AtrousRec*& buf)
+{
+    if (bytes > c->atrous_cap) {
+        HIP_TRY(hipStreamSynchronize(stream));  // ordered after every earlier use (begin_on)
+        (void)hipFree(c->atrous_buf);
+        c->atrous_buf = nullptr;
+        c->atrous_cap = 0;
+        HIP_TRY(hipMalloc((void**)&c->atrous_buf, bytes));
+        c->atrous_cap = bytes;
+    }
+    buf = bytes ? c->atrous_buf : nullptr;
+    return RT_OK;
+}
+
+int rt_denoise_atrous(rt_ctx* c, const rt_atrous_params* p, const void* mean, const double* stderr_map,
+                      const rt_denoise_guides* g, void* out, double* stderr_out)
+{
+    if (!c) return fail(RT_ERR_INVALID, "null argument");
+    rtk::DenoiseGuides G;
+    if (const char* bad = rtk::atrous_check(p, mean, stderr_map, g, out, stderr_out, G)) return fail(RT_ERR_INVALID, bad);
+    const bool f64 = p->format == RT_OUT_F64, on_dev = p->on_device != 0;
+    const size_t hw = (size_t)p->width * (size_t)p->height;
+    const size_t frame_bytes = hw * 3 * (f64 ? 8 : 4), se_bytes = hw * sizeof(double);
+    const size_t scratch_bytes = (size_t)rtk::atrous_state_buffers(p->levels) * hw * sizeof(rtk::AtrousRec);
+
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = p->stream ? (hipStream_t)p->stream : c->stream;
+    StreamScope scope(c, stream);
+    int rc = scope.begin();
+    if (rc) return rc;
+    rtk::AtrousRec* scratch = nullptr;
+    rc = atrous_scratch(c, stream, scratch_bytes, scratch);
+    if (rc) return rc;
+
+    // host pointers: the frame, the map, the results and the guides staged in one device block of the call's own
+    DeviceBlock blk;
+    const void* d_mean = mean;
+    const double* d_se = stderr_map;
+    void* d_out = out;
+    double* d_se_out = stderr_out;
+    if (!on_dev) {
+        const size_t g3 = align_up(hw * 3 * sizeof(double), 256), g1 = align_up(se_bytes, 256);
+        const size_t off_se = align_up(frame_bytes, 256), off_out = off_se + g1;
+        const size_t off_so = off_out + align_up(frame_bytes, 256), off_ga = off_so + (stderr_out ? g1 : 0);
+        const size_t off_gn = off_ga + (G.albedo ? g3 : 0), off_gz = off_gn + (G.normal ? g3 : 0);
+        HIP_TRY(hipMalloc(&blk.p, off_gz + (G.depth ? g1 : 0) + 256));
+        d_mean = blk.p;
+        d_se = (const double*)((char*)blk.p + off_se);
+        d_out = (char*)blk.p + off_out;
+        if (stderr_out) d_se_out = (double*)((char*)blk.p + off_so);
+        HIP_TRY(hipMemcpyAsync(blk.p, mean, frame_bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync((void*)d_se, stderr_map, se_bytes, hipMemcpyHostToDevice, stream));
+        auto stage = [&](const double*& guide, size_t off, size_t bytes) {
+            if (!guide) return hipSuccess;
+            void* d = (char*)blk.p + off;
+            const hipError_t e = hipMemcpyAsync(d, guide, bytes, hipMemcpyHostToDevice, stream);
+            guide = (const double*)d;
+            return e;
+        };
+        HIP_TRY(stage(G.albedo, off_ga, hw * 3 * sizeof(double)));
+        HIP_TRY(stage(G.normal, off_gn, hw * 3 * sizeof(double)));
+        HIP_TRY(stage(G.depth, off_gz, se_bytes));
+    }
+    HIP_TRY(hipEventRecord(c->ev_at[0], stream));
+    HIP_TRY(rtk::launch_atrous(d_mean, d_se, d_out, d_se_out, f64, p->width, p->height, p->levels, p->sigma_l,
+                               p->demodulate ? G.albedo : nullptr, G, scratch, stream));
+    HIP_TRY(hipEventRecord(c->ev_at[1], stream));
+    c->wstats = rt_atrous_stats{};
+    c->wstats.levels = p->levels;
+    c->wstats.scratch_bytes = (int64_t)scratch_bytes;
+    c->pending_at = true;
+    if (!on_dev) {
+        HIP_TRY(hipMemcpyAsync(out, d_out, frame_bytes, hipMemcpyDeviceToHost, stream));
+        if (stderr_out) HIP_TRY(hipMemcpyAsync(stderr_out, d_se_out, se_bytes, hipMemcpyDeviceToHost, stream));
+    }
+    rc = scope.end();
+    if (rc) return rc;
+    if (!on_dev) HIP_TRY(hipStreamSynchronize(stream));   // (the block is freed once its copies are done)
+    return RT_OK;
+}
+
+int rt_atrous_last_stats(rt_ctx* c, rt_atrous_stats* out)
+{
+    if (!c || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (c->pending_at) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipEventSynchronize(c->ev_at[1]));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_at[0], c->ev_at[1]));
+        c->wstats.kernel_ms = ms;
+        c->pending_at = false;
+    }
+    *out = c->wstats;
     return RT_OK;
 }
 

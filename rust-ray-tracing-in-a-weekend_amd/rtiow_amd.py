@@ -82,6 +82,7 @@ EXPORTED = [
     "rt_render_adaptive", "rt_adaptive_last_stats", "rt_adaptive_tile_errors_host",
     "rt_denoise", "rt_denoise_host", "rt_denoise_last_stats",
     "rt_render_features", "rt_features_last_stats", "rt_denoise_guided", "rt_denoise_guided_host",
+    "rt_denoise_atrous", "rt_denoise_atrous_host", "rt_atrous_last_stats",
 ]
 
 # int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_total)
@@ -231,6 +232,28 @@ class DenoiseGuides(ctypes.Structure):
 # loosest corner of that grid (profiles/guided_sweep_c2.json)
 GUIDE_SIGMAS = (0.4, 0.4, 0.4)
 
+
+class AtrousParams(ctypes.Structure):
+    """rt_atrous_params."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("format", ctypes.c_int32),
+                ("on_device", ctypes.c_int32), ("levels", ctypes.c_int32), ("demodulate", ctypes.c_int32),
+                ("sigma_l", ctypes.c_double), ("stream", ctypes.c_void_p)]
+
+
+class AtrousStats(ctypes.Structure):
+    """rt_atrous_stats: the last rt_denoise_atrous of a context."""
+    _fields_ = [("kernel_ms", ctypes.c_double), ("levels", ctypes.c_int32), ("scratch_bytes", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# rt_denoise_atrous's defaults (levels, sigma_l), with demodulate off: the lowest RMSE of the sweep
+# over {3, 4, 5} x {1, 2, 4, 8} x {off, on} on C2 at threshold 0.02, guides at 16 spp with
+# GUIDE_SIGMAS (DESIGN.md 5.11, profiles/atrous_sweep_c2.json)
+ATROUS_LEVELS = 3
+ATROUS_SIGMA_L = 2.0
+
 _lib = None
 
 
@@ -313,6 +336,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_features_last_stats": ([P, ctypes.POINTER(FeaturesStats)], I),
         "rt_denoise_guided": ([P, ctypes.POINTER(DenoiseParams), P, P, ctypes.POINTER(DenoiseGuides), P], I),
         "rt_denoise_guided_host": ([ctypes.POINTER(DenoiseParams), P, P, ctypes.POINTER(DenoiseGuides), P], I),
+        "rt_denoise_atrous": ([P, ctypes.POINTER(AtrousParams), P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
+        "rt_denoise_atrous_host": ([ctypes.POINTER(AtrousParams), P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
+        "rt_atrous_last_stats": ([P, ctypes.POINTER(AtrousStats)], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name, None)
@@ -690,6 +716,30 @@ def denoise_guided_host(mean, se, albedo=None, normal=None, depth=None, sigmas=G
     return out
 
 
+def _atrous_args(mean, se, levels, sigma_l, demodulate):
+    """(params, mean, se) of a host-pointer a-trous call: mean and se as _denoise_args takes them."""
+    d, m, s = _denoise_args(mean, se, 1, 0, 1.0)
+    return AtrousParams(d.width, d.height, d.format, 0, int(levels), int(demodulate), float(sigma_l), None), m, s
+
+
+def denoise_atrous_host(mean, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
+                        levels: int = ATROUS_LEVELS, sigma_l: float = ATROUS_SIGMA_L, demodulate: bool = False,
+                        want_stderr: bool = True):
+    """rt_denoise_atrous_host: the variance-guided a-trous wavelet filter (rt_abi.h) on the host, no
+    device needed. mean, se and the guides as denoise_guided_host takes them; demodulate filters
+    colour / albedo (needs albedo). Returns (the filtered frame in mean's format, the standard error
+    left in it, height x width f64, or None without want_stderr)."""
+    lib = load_library()
+    p, m, s = _atrous_args(mean, se, levels, sigma_l, demodulate)
+    g, keep = _guide_args(m.shape[:2], albedo, normal, depth, sigmas)
+    out = np.empty_like(m)
+    se_out = np.empty_like(s) if want_stderr else None
+    _check(lib.rt_denoise_atrous_host(ctypes.byref(p), m.ctypes.data, s.ctypes.data, ctypes.byref(g), out.ctypes.data,
+                                      se_out.ctypes.data if want_stderr else None), "rt_denoise_atrous_host")
+    del keep
+    return out, se_out
+
+
 def write_ppm(rgb: np.ndarray, path: str, samples_per_pixel: int = 1) -> None:
     """P3 writer of the reference (write_color, math.rs:119-132; main.rs:472, 591-596):
     height x width x 3, row 0 = bottom. An f64 array takes rt_write_ppm_f64 — the reference's
@@ -863,6 +913,42 @@ class Renderer:
         _check(self.lib.rt_denoise_guided(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr),
                                           ctypes.c_void_p(stderr_ptr), ctypes.byref(g), ctypes.c_void_p(out_ptr)),
                "rt_denoise_guided")
+
+    def denoise_atrous(self, mean, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
+                       levels: int = ATROUS_LEVELS, sigma_l: float = ATROUS_SIGMA_L, demodulate: bool = False,
+                       want_stderr: bool = True):
+        """rt_denoise_atrous on host arrays (synchronous): the a-trous wavelet filter with the feature
+        buffers of render_features as edge stops (None leaves one out); demodulate filters colour /
+        albedo. Returns (the filtered frame, the standard error left in it or None)."""
+        p, m, s = _atrous_args(mean, se, levels, sigma_l, demodulate)
+        g, keep = _guide_args(m.shape[:2], albedo, normal, depth, sigmas)
+        out = np.empty_like(m)
+        se_out = np.empty_like(s) if want_stderr else None
+        _check(self.lib.rt_denoise_atrous(self.h, ctypes.byref(p), m.ctypes.data, s.ctypes.data, ctypes.byref(g),
+                                          out.ctypes.data, se_out.ctypes.data if want_stderr else None),
+               "rt_denoise_atrous")
+        del keep
+        return out, se_out
+
+    def denoise_atrous_device(self, mean_ptr: int, stderr_ptr: int, out_ptr: int, width: int, height: int,
+                              albedo_ptr: int = 0, normal_ptr: int = 0, depth_ptr: int = 0, sigmas=GUIDE_SIGMAS,
+                              out_format: int = RT_OUT_F32, levels: int = ATROUS_LEVELS,
+                              sigma_l: float = ATROUS_SIGMA_L, demodulate: bool = False, stderr_out_ptr: int = 0,
+                              stream: Optional[int] = None):
+        """Enqueues rt_denoise_atrous over device buffers on `stream`: as denoise_guided_device;
+        stderr_out_ptr (height x width f64; 0 leaves it out) receives the standard error left."""
+        p = AtrousParams(int(width), int(height), int(out_format), 1, int(levels), int(demodulate), float(sigma_l),
+                         stream)
+        sa, sn, sz = (float(v) for v in sigmas)
+        g = DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+        _check(self.lib.rt_denoise_atrous(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr),
+                                          ctypes.c_void_p(stderr_ptr), ctypes.byref(g), ctypes.c_void_p(out_ptr),
+                                          ctypes.c_void_p(stderr_out_ptr or None)), "rt_denoise_atrous")
+
+    def atrous_stats(self) -> AtrousStats:
+        s = AtrousStats()
+        _check(self.lib.rt_atrous_last_stats(self.h, ctypes.byref(s)), "rt_atrous_last_stats")
+        return s
 
     def render_features(self, camera: Camera, params: RenderParams, albedo: bool = True, normal: bool = True,
                         depth: bool = True):

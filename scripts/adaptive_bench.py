@@ -25,10 +25,14 @@ rt_denoise_guided with the feature buffers (at --features SPP, default 16) and t
 normal, depth); rmse_guided is reported beside rmse and rmse_denoised, against the same reference,
 with the guided kernel's time. --parent-denoise: the parent library filters its uniform frame too
 (the plain filter's time on the commit before).
+--atrous LEVELS SIGMA_L: the same frame also goes through rt_denoise_atrous with the feature buffers
+(at --features SPP, default 16; the --guided sigmas, else the binding's) as edge stops; rmse_atrous,
+the summed level kernels' time and the mean of the filter's stderr_out are reported beside the
+others. --demodulate (with --atrous): it filters colour / albedo.
 
 usage: python scripts/adaptive_bench.py --config C2 --thresholds 0.02 0.01 0.005 \
            [--parent lib/librtiow_parent.so] [--min-spp 64 --step-spp 64] [--denoise 10 3 0.45]
-           [--features 16] [--guided 0.1 0.2 0.1] [--parent-denoise]
+           [--features 16] [--guided 0.1 0.2 0.1] [--parent-denoise] [--atrous 5 4.0 [--demodulate]]
            [--out adaptive_c2.json]
 """
 import argparse
@@ -67,6 +71,7 @@ if a["ref"]:
 res = {{}}
 dn = a.get("denoise")
 ft, gd = a.get("features"), a.get("guided")
+at = a.get("atrous")
 uniform_se = []
 guides = []
 def features(d):
@@ -79,12 +84,23 @@ def features(d):
              features_spp=ft)
     if not guides:
         guides.append(g)
-def denoised(mode, img, se, d):
+def error_map(mode, se):
     if mode == "uniform":
         if not uniform_se:   # the same frame's error map: an adaptive call that never stops early
             p = rt.Renderer.params(W, H, spp, a["depth"], bg, 1, out_format=rt.RT_OUT_F32)
             uniform_se.append(r.render_adaptive(cam, p, a["min_spp"], a["step_spp"], 0.0)[3])
         se = uniform_se[0]
+    return se
+def atrous(mode, img, se, d):
+    se = error_map(mode, se)
+    t0 = time.perf_counter()
+    out, se_out = r.denoise_atrous(img, se, *guides[0], gd or rt.GUIDE_SIGMAS, int(at[0]), float(at[1]), bool(a.get("demodulate")))
+    d["atrous_wall_ms"] = (time.perf_counter() - t0) * 1e3
+    st = r.atrous_stats()
+    d.update(atrous_kernel_ms=st.kernel_ms, atrous_scratch_bytes=st.scratch_bytes, atrous_mean_stderr_out=float(se_out.mean()))
+    return out
+def denoised(mode, img, se, d):
+    se = error_map(mode, se)
     t0 = time.perf_counter()
     out = r.denoise(img, se, int(dn[0]), int(dn[1]), float(dn[2]))
     d["denoise_wall_ms"] = (time.perf_counter() - t0) * 1e3
@@ -120,12 +136,15 @@ for mode in a["modes"]:
         features(d)
     if dn:
         denoised(mode, img, se, d)
+    if at:
+        atrous(mode, img, se, d)
 for _ in range(a["reps"]):
     for mode in a["modes"]:
         img, se, d = run(mode)
         if ft:
             features(d)
         out, out_g = denoised(mode, img, se, d) if dn else (None, None)
+        out_a = atrous(mode, img, se, d) if at else None
         e = res.setdefault(mode, dict(runs=[]))
         e["runs"].append(d)
         if ref is not None and "rmse" not in e:
@@ -134,6 +153,8 @@ for _ in range(a["reps"]):
                 e["rmse_denoised"] = float(np.sqrt(np.mean((gamma(out) - ref) ** 2)))
             if out_g is not None:
                 e["rmse_guided"] = float(np.sqrt(np.mean((gamma(out_g) - ref) ** 2)))
+            if out_a is not None:
+                e["rmse_atrous"] = float(np.sqrt(np.mean((gamma(out_a) - ref) ** 2)))
 print("RESULT", json.dumps(res))
 print("BUILD", rt.build_info())
 """
@@ -162,11 +183,16 @@ def main():
     ap.add_argument("--guided", type=float, nargs=3, default=None, metavar=("SA", "SN", "SZ"),
                     help="with --denoise: also filter with rt_denoise_guided (sigmas of albedo, normal, depth)")
     ap.add_argument("--parent-denoise", action="store_true", help="the parent library runs the plain filter too")
+    ap.add_argument("--atrous", type=float, nargs=2, default=None, metavar=("LEVELS", "SIGMA_L"),
+                    help="also filter every frame with rt_denoise_atrous (guided by the feature buffers)")
+    ap.add_argument("--demodulate", action="store_true", help="with --atrous: filter colour / albedo")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.guided and not a.denoise:
         ap.error("--guided needs --denoise R F K")
-    if a.guided and not a.features:
+    if a.demodulate and not a.atrous:
+        ap.error("--demodulate needs --atrous LEVELS SIGMA_L")
+    if (a.guided or a.atrous) and not a.features:
         a.features = 16
     cfg = CONFIGS[a.config]
     tmp = tempfile.TemporaryDirectory()   # the error reference: rendered by the first child, read by the others
@@ -182,7 +208,7 @@ def main():
             if a.denoise and (name == "new" or a.parent_denoise):
                 args["denoise"] = a.denoise
             if name == "new":
-                args.update(features=a.features, guided=a.guided)
+                args.update(features=a.features, guided=a.guided, atrous=a.atrous, demodulate=a.demodulate)
             env = dict(os.environ, RT_LIB_PATH=os.path.abspath(os.path.join(REPO, lib)))
             out = subprocess.run([sys.executable, "-c", CHILD.format(repo=REPO, args=json.dumps(args))], env=env,
                                  capture_output=True, text=True, timeout=900)
@@ -195,7 +221,7 @@ def main():
                 print(f"  {name}: rt_build_info {builds[name]}", flush=True)
             for mode, e in d.items():
                 k = runs.setdefault(f"{name}:{mode}", dict(runs=[], rmse=e.get("rmse"), rmse_denoised=e.get("rmse_denoised"),
-                                                           rmse_guided=e.get("rmse_guided")))
+                                                           rmse_guided=e.get("rmse_guided"), rmse_atrous=e.get("rmse_atrous")))
                 k["runs"] += e["runs"]
                 print(f"  {name}:{mode}: wall {['%.2f' % x['wall_ms'] for x in e['runs']]}", flush=True)
     uniform_px = cfg["width"] * cfg["height"] * cfg["spp"]
@@ -225,6 +251,13 @@ def main():
         if "guided_kernel_ms" in rs[0]:
             s.update(rmse_guided=e["rmse_guided"], guided_kernel_ms=median([x["guided_kernel_ms"] for x in rs]),
                      guided_wall_ms=median([x["guided_wall_ms"] for x in rs]), guided_sigmas=a.guided)
+        if "atrous_kernel_ms" in rs[0]:
+            s.update(rmse_atrous=e["rmse_atrous"], atrous_kernel_ms=median([x["atrous_kernel_ms"] for x in rs]),
+                     atrous_kernel_ms_min=min(x["atrous_kernel_ms"] for x in rs),
+                     atrous_kernel_ms_max=max(x["atrous_kernel_ms"] for x in rs),
+                     atrous_wall_ms=median([x["atrous_wall_ms"] for x in rs]), atrous=a.atrous, demodulate=int(a.demodulate),
+                     atrous_scratch_bytes=rs[0]["atrous_scratch_bytes"],
+                     atrous_mean_stderr_out=median([x["atrous_mean_stderr_out"] for x in rs]))
         for k in ("passes", "classify_ms", "mean_tile_spp", "tiles_at_max", "tiles_at_min", "tiles", "schedule", "n_batches",
                   "max_pass_batches"):
             if k in rs[0]:
@@ -239,6 +272,8 @@ def main():
             doc["features_spp"] = a.features
         if a.guided:
             doc["guided"] = a.guided
+        if a.atrous:
+            doc.update(atrous=a.atrous, demodulate=int(a.demodulate))
         json.dump(doc, open(a.out, "w"), indent=1)
 
 
