@@ -1,6 +1,7 @@
-// atrous.hpp — what the C ABI (abi.cpp) needs of the a-trous filter's two halves: the parameter
-// check and the error hook of atrous_host.cpp (plain C++, links without HIP, without abi.cpp and
-// without denoise_host.cpp) and the launcher of atrous_kernel.hip.
+// atrous.hpp — what the C ABI (abi_filters.cpp) needs of the a-trous filter's two halves: the
+// parameter check of atrous_host.cpp (plain C++, links without HIP, without denoise_host.cpp and
+// without the rest of the library) and the launcher of atrous_kernel.hip. (The host entry's error
+// hook: filter_guides.hpp.)
 #pragma once
 
 #include "rt/rt_abi.h"
@@ -13,10 +14,6 @@ namespace rtk {
 // G = the frames and 1 / sigma^2 of each guide given.
 const char* atrous_check(const rt_atrous_params* p, const void* mean, const double* stderr_map,
                          const rt_denoise_guides* g, const void* out, const double* stderr_out, DenoiseGuides& G);
-
-// Where rt_denoise_atrous_host reports its error text. abi.cpp points it at rt_last_error's slot
-// when the library loads; a program that links atrous_host.cpp alone leaves it null.
-extern void (*atrous_error_sink)(const char* msg);
 
 // state buffers a call of `levels` levels needs: 0, 1 or 2 (frame-sized arrays of AtrousRec)
 inline int atrous_state_buffers(int levels) { return levels <= 1 ? 0 : levels == 2 ? 1 : 2; }

@@ -8,10 +8,9 @@
 #include "rt/rt_abi.h"
 #include "atrous.hpp"
 #include "atrous_core.hpp"
+#include "filter_guides.hpp"
 
 namespace rtk {
-
-void (*atrous_error_sink)(const char* msg) = nullptr;
 
 const char* atrous_check(const rt_atrous_params* p, const void* mean, const double* stderr_map,
                          const rt_denoise_guides* g, const void* out, const double* stderr_out, DenoiseGuides& G)
@@ -26,26 +25,10 @@ const char* atrous_check(const rt_atrous_params* p, const void* mean, const doub
     if (!(p->sigma_l > 0.0) || !denoise_finite(p->sigma_l)) return "sigma_l must be greater than 0 and finite";
     if (p->demodulate != 0 && p->demodulate != 1) return "demodulate must be 0 or 1";
     if (p->demodulate && (!g || !g->albedo)) return "demodulate needs an albedo guide";
-    if (!g) return nullptr;
-    auto bad = [](double s) { return !(s > 0.0) || !denoise_finite(s); };
-    if ((g->albedo && bad(g->sigma_albedo)) || (g->normal && bad(g->sigma_normal)) || (g->depth && bad(g->sigma_depth)))
-        return "the sigma of every guide given must be greater than 0 and finite";
-    G.albedo = g->albedo;
-    G.normal = g->normal;
-    G.depth = g->depth;
-    if (g->albedo) G.ia = 1.0 / (g->sigma_albedo * g->sigma_albedo);
-    if (g->normal) G.in = 1.0 / (g->sigma_normal * g->sigma_normal);
-    if (g->depth) G.iz = 1.0 / (g->sigma_depth * g->sigma_depth);
-    return nullptr;
+    return guides_check(g, G);
 }
 
 namespace {
-
-int atrous_fail(int code, const char* msg)
-{
-    if (atrous_error_sink) atrous_error_sink(msg);
-    return code;
-}
 
 // a level's view of a frame of state records
 struct StateAccess {
@@ -93,12 +76,12 @@ extern "C" int rt_denoise_atrous_host(const rt_atrous_params* p, const void* mea
 {
     rtk::DenoiseGuides G;
     if (const char* bad = rtk::atrous_check(p, mean, stderr_map, g, out, stderr_out, G))
-        return rtk::atrous_fail(RT_ERR_INVALID, bad);
+        return rtk::filter_fail(RT_ERR_INVALID, bad);
     try {
         if (p->format == RT_OUT_F64) rtk::filter<double>(*p, (const double*)mean, stderr_map, G, (double*)out, stderr_out);
         else rtk::filter<float>(*p, (const float*)mean, stderr_map, G, (float*)out, stderr_out);
     } catch (const std::bad_alloc&) {
-        return rtk::atrous_fail(RT_ERR_OOM, "rt_denoise_atrous_host: frame-sized state arrays");
+        return rtk::filter_fail(RT_ERR_OOM, "rt_denoise_atrous_host: frame-sized state arrays");
     }
     return RT_OK;
 }

@@ -32,14 +32,6 @@
 
 namespace {
 
-using rtx::fail;
-
-#define HIP_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t e_ = (expr);                                \
-        if (e_ != hipSuccess) return rtx::hip_fail(e_, #expr); \
-    } while (0)
-
 // ---- RCCL, resolved at run time ------------------------------------------------------------------
 struct Rccl {
     void* h = nullptr;
@@ -115,35 +107,15 @@ struct rt_comm {
     ncclComm_t nc = nullptr;
     // this rank's tile slab (+ an 8-byte status trailer, sent with it), rank 0's gathered slabs,
     // rank 0's frame for a host-bound result, and the tile-cost vector of rt_comm_tile_order
-    void* slab = nullptr;
-    size_t slab_cap = 0;
-    void* recv = nullptr;
-    size_t recv_cap = 0;
-    void* stage = nullptr;
-    size_t stage_cap = 0;
-    uint64_t* cost = nullptr;
-    size_t cost_cap = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // render start / end, gathered, assembled
+    DevBuf slab, recv, stage, cost;   // (grown on demand, after the stream's earlier frames: no one still reads them)
+    EventSpan<4> ev;            // render start / end, gathered, assembled; armed: a gather's events not yet read into stats
     rt_comm_stats stats{};
-    bool pending = false;       // a gather's events not yet read into stats
     bool direct = false;        // the last frame was a world-1 direct render (no slabs gathered)
     size_t status_off = 0;      // byte offset of the status trailer in a slab (rank 0: to check the peers')
     size_t slab_stride = 0;     // bytes per rank in recv
 };
 
 namespace {
-
-int grow(hipStream_t s, void*& buf, size_t& cap, size_t need)
-{
-    if (need <= cap) return RT_OK;
-    HIP_TRY(hipStreamSynchronize(s));   // no earlier frame still reads it
-    (void)hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(&buf, need));
-    cap = need;
-    return RT_OK;
-}
 
 bool bad_frame(const rt_render_params* p)
 {
@@ -183,7 +155,7 @@ int shard_of(const rt_comm* m, const rt_render_params* p, hipStream_t s, Shard& 
 
 hipStream_t stream_of(const rt_comm* m, const rt_render_params* p)
 {
-    return p && p->stream ? (hipStream_t)p->stream : rtx::ctx_stream(m->ctx);
+    return p && p->stream ? (hipStream_t)p->stream : m->ctx->stream;
 }
 
 // Renders this rank's shard into its slab and writes the status trailer (0, or -rc when the
@@ -192,17 +164,17 @@ hipStream_t stream_of(const rt_comm* m, const rt_render_params* p)
 int enqueue_shard(rt_comm* m, const rt_camera* cam, const Shard& f, hipStream_t s)
 {
     HIP_TRY(hipSetDevice(m->device));
-    int rc = grow(s, m->slab, m->slab_cap, f.slab_bytes);
+    int rc = m->slab.reserve(s, f.slab_bytes);
     if (rc) return rc;
     if (m->rank == 0) {
-        rc = grow(s, m->recv, m->recv_cap, f.slab_bytes * (size_t)m->world);
+        rc = m->recv.reserve(s, f.slab_bytes * (size_t)m->world);
         if (rc) return rc;
     }
-    HIP_TRY(hipEventRecord(m->ev[0], s));
-    rc = rt_render(m->ctx, cam, &f.q, m->slab);
+    HIP_TRY(m->ev.record(0, s));
+    rc = rt_render(m->ctx, cam, &f.q, m->slab.p);
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipEventRecord(m->ev[1], s));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)((char*)m->slab + f.slab_bytes - 8), rc ? -rc : 0, 2, s));
+    HIP_TRY(m->ev.record(1, s));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->slab.as<char>() + f.slab_bytes - 8), rc ? -rc : 0, 2, s));
     m->status_off = f.slab_bytes - 8;
     m->slab_stride = f.slab_bytes;
     return rc;
@@ -210,8 +182,8 @@ int enqueue_shard(rt_comm* m, const rt_camera* cam, const Shard& f, hipStream_t 
 
 int enqueue_gather(const Rccl& R, rt_comm* m, const Shard& f, hipStream_t s)
 {
-    NCCL_TRY(R, R.Gather(m->slab, m->rank == 0 ? m->recv : nullptr, f.slab_bytes, ncclUint8, 0, m->nc, s));
-    HIP_TRY(hipEventRecord(m->ev[2], s));
+    NCCL_TRY(R, R.Gather(m->slab.p, m->rank == 0 ? m->recv.p : nullptr, f.slab_bytes, ncclUint8, 0, m->nc, s));
+    HIP_TRY(m->ev.record(2, s));
     return RT_OK;
 }
 
@@ -219,18 +191,16 @@ int enqueue_gather(const Rccl& R, rt_comm* m, const Shard& f, hipStream_t s)
 // copied to the caller's host memory), in the context's tile order.
 int enqueue_assemble(rt_comm* m, const rt_render_params* p, const Shard& f, hipStream_t s, void* frame)
 {
-    int64_t n_order = 0;
-    const uint32_t* order = rtx::ctx_tile_order(m->ctx, &n_order);
     const size_t frame_bytes = (size_t)p->width * p->height * 3 * f.esz;
     void* dst = frame;
     if (!p->out_on_device) {
-        const int rc = grow(s, m->stage, m->stage_cap, frame_bytes);
+        const int rc = m->stage.reserve(s, frame_bytes);
         if (rc) return rc;
-        dst = m->stage;
+        dst = m->stage.p;
     }
-    HIP_TRY(rtk::launch_assemble_tiles(m->recv, dst, f.esz == 8, m->world, (long long)(f.slab_bytes / f.esz),
-                                       p->width, p->height, n_order > 0 ? order : nullptr, s));
-    HIP_TRY(hipEventRecord(m->ev[3], s));
+    HIP_TRY(rtk::launch_assemble_tiles(m->recv.p, dst, f.esz == 8, m->world, (long long)(f.slab_bytes / f.esz),
+                                       p->width, p->height, m->ctx->tile_order.as<uint32_t>(), s));
+    HIP_TRY(m->ev.record(3, s));
     if (!p->out_on_device) HIP_TRY(hipMemcpyAsync(frame, dst, frame_bytes, hipMemcpyDeviceToHost, s));
     return RT_OK;
 }
@@ -240,7 +210,7 @@ int peer_status(rt_comm* m)
 {
     for (int r = 0; r < m->world; ++r) {
         int32_t st = 0;
-        HIP_TRY(hipMemcpy(&st, (char*)m->recv + (size_t)r * m->slab_stride + m->status_off, 4,
+        HIP_TRY(hipMemcpy(&st, m->recv.as<char>() + (size_t)r * m->slab_stride + m->status_off, 4,
                           hipMemcpyDeviceToHost));
         if (st != 0)
             return fail(RT_ERR_PEER, "rank " + std::to_string(r) + "'s shard render failed (" + std::to_string(-st) +
@@ -251,7 +221,7 @@ int peer_status(rt_comm* m)
 
 void note_gather(rt_comm* m, const Shard& f)
 {
-    m->pending = true;
+    m->ev.arm();
     m->direct = false;
     m->stats.slab_bytes = (int64_t)f.slab_bytes;
     m->stats.tiles = f.n_mine;
@@ -263,9 +233,7 @@ void note_gather(rt_comm* m, const Shard& f)
 // profiles/r06e_c2_*.log). The stats' gather and assemble times are 0.
 bool direct_ok(const rt_comm* m)
 {
-    int64_t n_order = 0;
-    (void)rtx::ctx_tile_order(m->ctx, &n_order);
-    return m->world == 1 && n_order == 0 && rtx::ctx_comm_direct(m->ctx);
+    return m->world == 1 && m->ctx->tile_order_n == 0 && m->ctx->opt_comm_direct != 0;
 }
 
 int render_direct(rt_comm* m, const rt_camera* cam, const rt_render_params* p, hipStream_t s, void* frame)
@@ -278,11 +246,11 @@ int render_direct(rt_comm* m, const rt_camera* cam, const rt_render_params* p, h
     q.tile_shard = 0;
     q.stream = s;
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipEventRecord(m->ev[0], s));
+    HIP_TRY(m->ev.record(0, s));
     const int rc = rt_render(m->ctx, cam, &q, frame);
     HIP_TRY(hipSetDevice(m->device));
-    for (int i = 1; i < 4; ++i) HIP_TRY(hipEventRecord(m->ev[i], s));
-    m->pending = true;
+    for (int i = 1; i < 4; ++i) HIP_TRY(m->ev.record(i, s));
+    m->ev.arm();
     m->direct = true;
     m->stats.slab_bytes = 0;
     m->stats.tiles = rt_tiles_in_shard(p->width, p->height, 0, 1);
@@ -316,10 +284,10 @@ int cost_local(rt_comm* m, const rt_camera* cam, const rt_render_params* p, int 
     if (bad_frame(p) || cost_spp < 1) return fail(RT_ERR_INVALID, "bad render params or cost_spp");
     cp.n_tiles = (int64_t)((p->width + 7) / 8) * ((p->height + 7) / 8);
     HIP_TRY(hipSetDevice(m->device));
-    int rc = grow(s, (void*&)m->cost, m->cost_cap, (size_t)(cp.n_tiles + 1) * sizeof(uint64_t));
+    int rc = m->cost.reserve(s, (size_t)(cp.n_tiles + 1) * sizeof(uint64_t));
     if (rc) return rc;
-    cp.schedule = rtx::ctx_schedule(m->ctx);
-    cp.precision = rtx::ctx_precision(m->ctx);
+    cp.schedule = m->ctx->opt.schedule;
+    cp.precision = m->ctx->opt.precision;
     std::vector<uint64_t> h((size_t)cp.n_tiles + 1, 0);
     // raster shards, f64 (count_work's tile costs), a pool schedule (the chunk schedule counts none)
     rc = rt_ctx_set_tile_order(m->ctx, nullptr, 0);
@@ -331,8 +299,8 @@ int cost_local(rt_comm* m, const rt_camera* cam, const rt_render_params* p, int 
     q.count_work = 1;
     q.out_format = RT_OUT_F32;
     if (!rc) rc = shard_of(m, &q, s, f);
-    if (!rc) rc = grow(s, m->slab, m->slab_cap, f.slab_bytes);
-    if (!rc) rc = rt_render(m->ctx, cam, &f.q, m->slab);
+    if (!rc) rc = m->slab.reserve(s, f.slab_bytes);
+    if (!rc) rc = rt_render(m->ctx, cam, &f.q, m->slab.p);
     if (!rc) {
         const int got = rt_last_tile_costs(m->ctx, h.data(), cp.n_tiles);   // synchronizes the render
         if (got < 0) rc = got;
@@ -344,7 +312,7 @@ int cost_local(rt_comm* m, const rt_camera* cam, const rt_render_params* p, int 
     if (rc) std::fill(h.begin(), h.end(), 0);
     h[(size_t)cp.n_tiles] = rc ? 1 : 0;   // failures, summed over the ranks
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpyAsync(m->cost, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(m->cost.p, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));   // (h is pageable and local)
     return RT_OK;
 }
@@ -353,7 +321,7 @@ int cost_finish(rt_comm* m, hipStream_t s, CostPass& cp)
 {
     HIP_TRY(hipSetDevice(m->device));
     std::vector<uint64_t> h((size_t)cp.n_tiles + 1, 0);
-    HIP_TRY(hipMemcpyAsync(h.data(), m->cost, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h.data(), m->cost.p, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     int rc = RT_OK;
     if (h[(size_t)cp.n_tiles] != 0) {   // some rank's pass failed: every rank keeps raster order
@@ -395,14 +363,12 @@ static int comm_new(rt_ctx* ctx, int rank, int world, rt_comm** out)
     m->ctx = ctx;
     m->rank = rank;
     m->world = world;
-    m->device = rtx::ctx_device(ctx);
+    m->device = ctx->device;
     hipError_t e = hipSetDevice(m->device);
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&m->ev[i]);
+    if (e == hipSuccess) e = m->ev.create();
     if (e != hipSuccess) {
-        for (auto& v : m->ev)
-            if (v) (void)hipEventDestroy(v);
         delete m;
-        return rtx::hip_fail(e, "rt_comm events");
+        return hip_fail(e, "rt_comm events");
     }
     *out = m;
     return RT_OK;
@@ -439,7 +405,7 @@ int rt_comm_init_all(rt_ctx* const* ctxs, int n, rt_comm** comms_out)
     for (int i = 0; i < n; ++i) {
         comms_out[i] = nullptr;
         if (!ctxs[i]) return fail(RT_ERR_INVALID, "null context");
-        dev[(size_t)i] = rtx::ctx_device(ctxs[i]);
+        dev[(size_t)i] = ctxs[i]->device;
         for (int j = 0; j < i; ++j)
             if (dev[(size_t)j] == dev[(size_t)i]) return fail(RT_ERR_INVALID, "two contexts on one device");
     }
@@ -464,20 +430,14 @@ void rt_comm_destroy(rt_comm* m)
 {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    for (auto& e : m->ev)
-        if (e) (void)hipEventSynchronize(e);
-    (void)hipStreamSynchronize(rtx::ctx_stream(m->ctx));
+    for (int i = 0; i < 4; ++i)
+        if (m->ev.ev[i]) (void)m->ev.wait(i);
+    (void)hipStreamSynchronize(m->ctx->stream);
     if (m->nc) {
         const Rccl& R = rccl();
         if (R.CommDestroy) (void)R.CommDestroy(m->nc);
     }
-    (void)hipFree(m->slab);
-    (void)hipFree(m->recv);
-    (void)hipFree(m->stage);
-    (void)hipFree(m->cost);
-    for (auto& e : m->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete m;
+    delete m;   // (the buffers and events free themselves)
 }
 
 int rt_comm_rank(const rt_comm* m, int* rank, int* world)
@@ -498,7 +458,7 @@ int rt_comm_tile_order(rt_comm* m, const rt_camera* cam, const rt_render_params*
     CostPass cp;
     rc = cost_local(m, cam, p, cost_spp, s, cp);
     if (rc) return rc;
-    NCCL_TRY(*R, R->AllReduce(m->cost, m->cost, (size_t)cp.n_tiles + 1, ncclUint64, ncclSum, m->nc, s));
+    NCCL_TRY(*R, R->AllReduce(m->cost.p, m->cost.p, (size_t)cp.n_tiles + 1, ncclUint64, ncclSum, m->nc, s));
     return cost_finish(m, s, cp);
 }
 
@@ -514,14 +474,14 @@ int rt_comm_tile_order_all(rt_comm* const* comms, int n, const rt_camera* cam, c
     if (rc) return rc;
     std::vector<CostPass> cp((size_t)n);
     for (int i = 0; i < n; ++i) {
-        rc = cost_local(comms[i], cam, p, cost_spp, rtx::ctx_stream(comms[i]->ctx), cp[(size_t)i]);
+        rc = cost_local(comms[i], cam, p, cost_spp, comms[i]->ctx->stream, cp[(size_t)i]);
         if (rc) return rc;
     }
     NCCL_TRY(*R, R->GroupStart());
     for (int i = 0; i < n; ++i) {
         rt_comm* m = comms[i];
-        const ncclResult_t r = R->AllReduce(m->cost, m->cost, (size_t)cp[(size_t)i].n_tiles + 1, ncclUint64, ncclSum,
-                                            m->nc, rtx::ctx_stream(m->ctx));
+        const ncclResult_t r = R->AllReduce(m->cost.p, m->cost.p, (size_t)cp[(size_t)i].n_tiles + 1, ncclUint64, ncclSum,
+                                            m->nc, m->ctx->stream);
         if (r != ncclSuccess) {
             (void)R->GroupEnd();
             return nccl_fail(*R, r, "ncclAllReduce");
@@ -530,7 +490,7 @@ int rt_comm_tile_order_all(rt_comm* const* comms, int n, const rt_camera* cam, c
     NCCL_TRY(*R, R->GroupEnd());
     int first = RT_OK;
     for (int i = 0; i < n; ++i) {
-        rc = cost_finish(comms[i], rtx::ctx_stream(comms[i]->ctx), cp[(size_t)i]);
+        rc = cost_finish(comms[i], comms[i]->ctx->stream, cp[(size_t)i]);
         if (rc && !first) first = rc;
     }
     return first;
@@ -549,7 +509,7 @@ int rt_render_gather(rt_comm* m, const rt_camera* cam, const rt_render_params* p
     rc = shard_of(m, p, s, f);   // (argument errors: every rank has the same p and fails alike)
     if (rc) return rc;
     const int rc_render = enqueue_shard(m, cam, f, s);
-    if (m->slab_cap < f.slab_bytes || (m->rank == 0 && m->recv_cap < f.slab_bytes * (size_t)m->world))
+    if (m->slab.cap < f.slab_bytes || (m->rank == 0 && m->recv.cap < f.slab_bytes * (size_t)m->world))
         return rc_render;   // no buffers to send from: nothing was enqueued for the peers either
     rc = enqueue_gather(*R, m, f, s);
     if (rc) return rc;
@@ -573,25 +533,25 @@ int rt_render_gather_all(rt_comm* const* comms, int n, const rt_camera* cam, con
     const Rccl* R;
     rc = load_rccl(R);
     if (rc) return rc;
-    if (n == 1 && direct_ok(comms[0])) return render_direct(comms[0], cam, p, rtx::ctx_stream(comms[0]->ctx), frame);
+    if (n == 1 && direct_ok(comms[0])) return render_direct(comms[0], cam, p, comms[0]->ctx->stream, frame);
     std::vector<Shard> f((size_t)n);
     for (int i = 0; i < n; ++i) {
-        rc = shard_of(comms[i], p, rtx::ctx_stream(comms[i]->ctx), f[(size_t)i]);
+        rc = shard_of(comms[i], p, comms[i]->ctx->stream, f[(size_t)i]);
         if (rc) return rc;
     }
     int rc_render = RT_OK;
     for (int i = 0; i < n; ++i) {   // every render enqueued before any gather: the GPUs trace at once
-        rc = enqueue_shard(comms[i], cam, f[(size_t)i], rtx::ctx_stream(comms[i]->ctx));
+        rc = enqueue_shard(comms[i], cam, f[(size_t)i], comms[i]->ctx->stream);
         if (rc && !rc_render) rc_render = rc;
-        if (comms[i]->slab_cap < f[(size_t)i].slab_bytes ||
-            (i == 0 && comms[0]->recv_cap < f[0].slab_bytes * (size_t)n))
+        if (comms[i]->slab.cap < f[(size_t)i].slab_bytes ||
+            (i == 0 && comms[0]->recv.cap < f[0].slab_bytes * (size_t)n))
             return rc;   // no buffers: nothing to gather
     }
     NCCL_TRY(*R, R->GroupStart());
     for (int i = 0; i < n; ++i) {
         rt_comm* m = comms[i];
-        const ncclResult_t r = R->Gather(m->slab, i == 0 ? m->recv : nullptr, f[(size_t)i].slab_bytes, ncclUint8, 0,
-                                         m->nc, rtx::ctx_stream(m->ctx));
+        const ncclResult_t r = R->Gather(m->slab.p, i == 0 ? m->recv.p : nullptr, f[(size_t)i].slab_bytes, ncclUint8, 0,
+                                         m->nc, m->ctx->stream);
         if (r != ncclSuccess) {
             (void)R->GroupEnd();
             return nccl_fail(*R, r, "ncclGather");
@@ -600,16 +560,16 @@ int rt_render_gather_all(rt_comm* const* comms, int n, const rt_camera* cam, con
     NCCL_TRY(*R, R->GroupEnd());
     for (int i = 0; i < n; ++i) {
         HIP_TRY(hipSetDevice(comms[i]->device));
-        HIP_TRY(hipEventRecord(comms[i]->ev[2], rtx::ctx_stream(comms[i]->ctx)));
+        HIP_TRY(comms[i]->ev.record(2, comms[i]->ctx->stream));
         note_gather(comms[i], f[(size_t)i]);
     }
     HIP_TRY(hipSetDevice(comms[0]->device));
-    rc = enqueue_assemble(comms[0], p, f[0], rtx::ctx_stream(comms[0]->ctx), frame);
+    rc = enqueue_assemble(comms[0], p, f[0], comms[0]->ctx->stream, frame);
     if (rc) return rc;
     if (p->out_on_device) return rc_render;
     for (int i = 0; i < n; ++i) {
         HIP_TRY(hipSetDevice(comms[i]->device));
-        HIP_TRY(hipStreamSynchronize(rtx::ctx_stream(comms[i]->ctx)));
+        HIP_TRY(hipStreamSynchronize(comms[i]->ctx->stream));
     }
     if (rc_render) return rc_render;
     HIP_TRY(hipSetDevice(comms[0]->device));
@@ -619,15 +579,15 @@ int rt_render_gather_all(rt_comm* const* comms, int n, const rt_camera* cam, con
 int rt_comm_last_stats(rt_comm* m, rt_comm_stats* out)
 {
     if (!m || !out) return fail(RT_ERR_INVALID, "null argument");
-    if (m->pending) {
+    if (m->ev.pending) {   // (not resolve(): only rank 0 records the last event)
         HIP_TRY(hipSetDevice(m->device));
-        HIP_TRY(hipEventSynchronize(m->ev[2]));
+        HIP_TRY(m->ev.wait(2));
         float a = 0, b = 0, c = 0;
-        HIP_TRY(hipEventElapsedTime(&a, m->ev[0], m->ev[1]));
-        HIP_TRY(hipEventElapsedTime(&b, m->ev[1], m->ev[2]));
+        HIP_TRY(m->ev.elapsed(0, &a));
+        HIP_TRY(m->ev.elapsed(1, &b));
         if (m->rank == 0) {
-            HIP_TRY(hipEventSynchronize(m->ev[3]));
-            HIP_TRY(hipEventElapsedTime(&c, m->ev[2], m->ev[3]));
+            HIP_TRY(m->ev.wait(3));
+            HIP_TRY(m->ev.elapsed(2, &c));
         }
         m->stats.render_ms = a;
         m->stats.gather_ms = b;
@@ -637,10 +597,10 @@ int rt_comm_last_stats(rt_comm* m, rt_comm_stats* out)
         m->stats.peer_failed = 0;
         for (int r = 0; m->rank == 0 && !m->direct && r < m->world; ++r) {
             int32_t v = 0;
-            HIP_TRY(hipMemcpy(&v, (char*)m->recv + (size_t)r * m->slab_stride + m->status_off, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&v, m->recv.as<char>() + (size_t)r * m->slab_stride + m->status_off, 4, hipMemcpyDeviceToHost));
             m->stats.peer_failed += v != 0;
         }
-        m->pending = false;
+        m->ev.disarm();
     }
     *out = m->stats;
     return RT_OK;
@@ -652,14 +612,13 @@ int rt_tiles_assemble(rt_ctx* ctx, const void* slabs, int64_t slab_elems, int wo
     if (!ctx || !slabs || !frame || world < 1 || bad_frame(p)) return fail(RT_ERR_INVALID, "bad argument");
     const int n_max = rt_tiles_in_shard(p->width, p->height, 0, world);
     if (n_max <= 0 || slab_elems < 192LL * n_max) return fail(RT_ERR_INVALID, "slab_elems below the largest shard's");
-    int64_t n_order = 0;
-    const uint32_t* order = rtx::ctx_tile_order(ctx, &n_order);
+    const int64_t n_order = ctx->tile_order_n;
     const int64_t n_tiles = (int64_t)((p->width + 7) / 8) * ((p->height + 7) / 8);
     if (n_order > 0 && n_order != n_tiles) return fail(RT_ERR_INVALID, "the context's tile order is for another frame");
-    HIP_TRY(hipSetDevice(rtx::ctx_device(ctx)));
-    const hipStream_t s = p->stream ? (hipStream_t)p->stream : rtx::ctx_stream(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t s = p->stream ? (hipStream_t)p->stream : ctx->stream;
     HIP_TRY(rtk::launch_assemble_tiles(slabs, frame, p->out_format == RT_OUT_F64, world, (long long)slab_elems,
-                                       p->width, p->height, n_order > 0 ? order : nullptr, s));
+                                       p->width, p->height, ctx->tile_order.as<uint32_t>(), s));
     return RT_OK;
 }
 

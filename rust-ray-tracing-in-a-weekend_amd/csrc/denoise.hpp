@@ -1,6 +1,7 @@
-// denoise.hpp — what the C ABI (abi.cpp) needs of the NL-means filter's two halves: the
-// parameter check and the error hook of denoise_host.cpp (plain C++, links without HIP and without
-// abi.cpp) and the launcher of denoise_kernel.hip.
+// denoise.hpp — what the C ABI (abi_filters.cpp) needs of the NL-means filter's two halves: the
+// parameter check of denoise_host.cpp (plain C++, links without HIP and without the rest of the
+// library) and the launcher of denoise_kernel.hip. (The guide check and the host entries' error
+// hook, shared with the a-trous filter: filter_guides.hpp.)
 #pragma once
 
 #include "rt/rt_abi.h"
@@ -11,14 +12,6 @@ namespace rtk {
 // rt_denoise's and rt_denoise_host's argument check: null when the call is valid, else the text
 // for rt_last_error (the code is RT_ERR_INVALID).
 const char* denoise_check(const rt_denoise_params* p, const void* mean, const double* stderr_map, const void* out);
-
-// rt_denoise_guided's guides: null when they are valid (g may be null: no guides), else the text;
-// G = the frames and 1 / sigma^2 of each guide given.
-const char* denoise_guides_check(const rt_denoise_guides* g, DenoiseGuides& G);
-
-// Where rt_denoise_host reports its error text. abi.cpp points it at rt_last_error's slot when
-// the library loads; a program that links denoise_host.cpp alone leaves it null.
-extern void (*denoise_error_sink)(const char* msg);
 
 }  // namespace rtk
 

@@ -9,10 +9,9 @@
 #include "rt/rt_abi.h"
 #include "denoise.hpp"
 #include "denoise_core.hpp"
+#include "filter_guides.hpp"
 
 namespace rtk {
-
-void (*denoise_error_sink)(const char* msg) = nullptr;
 
 const char* denoise_check(const rt_denoise_params* p, const void* mean, const double* stderr_map, const void* out)
 {
@@ -26,29 +25,7 @@ const char* denoise_check(const rt_denoise_params* p, const void* mean, const do
     return nullptr;
 }
 
-const char* denoise_guides_check(const rt_denoise_guides* g, DenoiseGuides& G)
-{
-    G = DenoiseGuides{};
-    if (!g) return nullptr;
-    auto bad = [](double s) { return !(s > 0.0) || !denoise_finite(s); };
-    if ((g->albedo && bad(g->sigma_albedo)) || (g->normal && bad(g->sigma_normal)) || (g->depth && bad(g->sigma_depth)))
-        return "the sigma of every guide given must be greater than 0 and finite";
-    G.albedo = g->albedo;
-    G.normal = g->normal;
-    G.depth = g->depth;
-    if (g->albedo) G.ia = 1.0 / (g->sigma_albedo * g->sigma_albedo);
-    if (g->normal) G.in = 1.0 / (g->sigma_normal * g->sigma_normal);
-    if (g->depth) G.iz = 1.0 / (g->sigma_depth * g->sigma_depth);
-    return nullptr;
-}
-
 namespace {
-
-int denoise_fail(int code, const char* msg)
-{
-    if (denoise_error_sink) denoise_error_sink(msg);
-    return code;
-}
 
 template <typename T>
 void filter(const rt_denoise_params& p, const T* M, const double* se, const DenoiseGuides& G, T* out)
@@ -112,14 +89,14 @@ void filter(const rt_denoise_params& p, const T* M, const double* se, const Deno
 extern "C" int rt_denoise_guided_host(const rt_denoise_params* p, const void* mean, const double* stderr_map,
                                       const rt_denoise_guides* g, void* out)
 {
-    if (const char* bad = rtk::denoise_check(p, mean, stderr_map, out)) return rtk::denoise_fail(RT_ERR_INVALID, bad);
+    if (const char* bad = rtk::denoise_check(p, mean, stderr_map, out)) return rtk::filter_fail(RT_ERR_INVALID, bad);
     rtk::DenoiseGuides G;
-    if (const char* bad = rtk::denoise_guides_check(g, G)) return rtk::denoise_fail(RT_ERR_INVALID, bad);
+    if (const char* bad = rtk::guides_check(g, G)) return rtk::filter_fail(RT_ERR_INVALID, bad);
     try {
         if (p->format == RT_OUT_F64) rtk::filter<double>(*p, (const double*)mean, stderr_map, G, (double*)out);
         else rtk::filter<float>(*p, (const float*)mean, stderr_map, G, (float*)out);
     } catch (const std::bad_alloc&) {
-        return rtk::denoise_fail(RT_ERR_OOM, "rt_denoise_host: frame-sized work arrays");
+        return rtk::filter_fail(RT_ERR_OOM, "rt_denoise_host: frame-sized work arrays");
     }
     return RT_OK;
 }
