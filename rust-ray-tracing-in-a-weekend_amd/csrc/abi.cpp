@@ -434,23 +434,14 @@ int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_
     double* const acc_tmp = c->acc_tmp.as<double>();
     double* const open = pl.open_chunk ? acc_tmp : nullptr;
     double* const acc = !pl.own_total ? sink.acc : pl.open_chunk ? acc_tmp + pl.px * 3 : acc_tmp;
-    rtk::SceneDev S = c->S;
-    S.n_lds_nodes = pl.n_lds_nodes;
-    S.n_lds_materials = pl.n_lds_materials;
-    S.n_lds_textures = pl.n_lds_textures;
-    S.n_lds_blas = pl.n_lds_blas;
-    S.seed_stage_bytes = (int32_t)pl.seed_stage_bytes;
+    PlannedLaunch launch = planned_launch(c->S, pl);
+    const rtk::SceneDev& S = launch.S;
     K.block_chunks = pl.block_chunks;
     K.block_samples = pl.block_samples;
     K.ring_waves = pl.ring_waves;
     int waves_per_simd = 0;
-    rtk::LaunchOpts o;
-    o.features = pl.features;
-    o.slab32 = pl.slab32;
-    o.lds_stack = pl.lds_stack;
+    rtk::LaunchOpts& o = launch.o;
     o.count = rq.count_work;
-    o.pool = pl.schedule;
-    o.f32 = pl.f32;
     o.waves_per_simd = &waves_per_simd;
     const rtk::SampleTiles tiles{lay.w, lay.rows, (lay.w + 7) / 8, pl.f32};
     rc = deal_setup(c, cam, p, pl, sink.moments != nullptr, img_tiles, stream, K);

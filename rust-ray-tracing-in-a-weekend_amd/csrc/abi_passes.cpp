@@ -262,18 +262,10 @@ int rt_render_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
     rtk::KParams K;
     rc = fill_kparams(c, cam, &rp, lay, chunk, Sink{}, img_tiles, K);
     if (rc) return rc;
-    rtk::SceneDev S = c->S;
-    S.n_lds_nodes = pl.n_lds_nodes;
-    S.n_lds_materials = pl.n_lds_materials;
-    S.n_lds_textures = pl.n_lds_textures;
-    S.n_lds_blas = pl.n_lds_blas;
-    rtk::LaunchOpts o;
-    o.features = pl.features;
-    o.slab32 = pl.slab32;
-    o.lds_stack = pl.lds_stack;
-    o.count = 0;
-    o.pool = RT_SCHED_CHUNKS;
-    o.f32 = 0;
+    // (the plan of the chunk schedule in f64: no staged sample starts, nothing counted)
+    const PlannedLaunch launch = planned_launch(c->S, pl);
+    const rtk::SceneDev& S = launch.S;
+    const rtk::LaunchOpts& o = launch.o;
 
     HIP_TRY(c->ev_ft.record(0, stream));
     for (int bi = 0; bi < n_batches; ++bi) {

@@ -13,12 +13,12 @@
 // (features_kernel.hip) adds the partials in chunk order. Plain vector stores, no atomics.
 //
 // Launch bounds, waves per SIMD and the LDS layout are the trace kernel's of the same
-// configuration (BlockThreads, min_waves, lds_layout), so a scene's LDS plan serves both. The
+// configuration (Cfg::SHAPE, lds_layout), so a scene's LDS plan serves both. The
 // walk (trace_world) sets the register pressure, not the loop around it: each variant compiles to
 // its trace_chunks twin's VGPR count, with about the same few dwords of scratch where that one
 // has them (the compiler's figures: DESIGN.md §5.10).
 #pragma once
-#include "trace_device.hpp"
+#include "trace_launch.hpp"
 #include "features_kernel.hpp"
 
 namespace rtk {
@@ -76,54 +76,27 @@ __global__ void __launch_bounds__(BlockThreads<C>(), min_waves<C>()) trace_featu
     o[6] = dz;
 }
 
-// The launch of one configuration: launch_one's chunk-schedule branch (the same workgroup, the
-// same dynamic LDS) for trace_features.
-template <uint32_t F, bool S32, bool LDS>
-static void launch_features_one(const Launch& L, hipStream_t stream, bool nall)
-{
-    const SceneDev& S = *L.S;
-    const bool s16 = RT_STACK16 && LDS && nall && S32 && F == FEAT_SET_SPHERES;   // Stack16Cfg
-    const int node_bytes = nall && S32 ? (int)sizeof(LdsNode) : (int)sizeof(rt_bvh_node);   // lds_node_bytes
-    const bool stage = F != FEAT_SET_SPHERES;                   // StageShade
-    const bool blas = RT_STAGE_BLAS && (F & FEAT_INST_BLAS) != 0;   // StageBlas
-    const int bt = block_threads_of(F, false, RT_STACK16 && LDS && nall && S32), wpb = bt / 64;   // BlockThreads
-    const size_t lds = lds_layout(S.n_lds_nodes, node_bytes, blas ? S.n_lds_blas : 0, LDS ? S.stack_entries : 0,
-                                  s16 ? 2 : 4, stage ? S.n_lds_materials : 0, stage ? S.n_lds_textures : 0, bt).total;
-    const unsigned nb = (unsigned)((L.n_blocks + wpb - 1) / wpb);
-    auto go = [&](auto kernel) {
-        if (L.waves_per_simd) (void)blocks_per_cu(L, kernel, lds, bt);
-        hipLaunchKernelGGL(kernel, dim3(nb), dim3(bt), lds, stream, S, L.P, L.out);
-    };
-    if (nall) go(trace_features<Cfg<F, S32, LDS, true, false, false>>);
-    else go(trace_features<Cfg<F, S32, LDS, false, false, false>>);
-}
-
-// One feature set's kernels (features_v_*.hip instantiate one each): launch_f's choice of the
-// instantiation — whole or partial TLAS in LDS, 16-bit stack entries only where they fit and the
-// kernel has no static LDS in front of the node records.
+// One feature set's kernels (features_v_*.hip instantiate one each): launch_variant's shape — whole
+// or partial TLAS in LDS, 16-bit stack entries only where they fit and the kernel has no static LDS
+// in front of the node records — and its chunk-schedule launch (the same workgroup, the same
+// dynamic LDS) for trace_features.
 template <uint32_t F>
 hipError_t launch_features_variant(const Launch& L, const LaunchOpts& o, hipStream_t stream)
 {
     const SceneDev& S = *L.S;
-    bool nall = S.n_lds_nodes > 0 && S.n_lds_nodes == S.n_tlas_nodes;
-    constexpr bool S16F = F == FEAT_SET_SPHERES;
-    if (RT_STACK16 && S16F && o.slab32 && o.lds_stack && !S.stack16_ok) nall = false;
-    if (RT_STACK16 && S16F && o.slab32 && o.lds_stack && nall) {
-        static int static_lds = -1;
-        if (static_lds < 0) {
-            hipFuncAttributes a;
-            static_lds = hipFuncGetAttributes(&a, (const void*)trace_features<Cfg<F, true, true, true, false, false>>) !=
-                                 hipSuccess || a.sharedSizeBytes != 0;
-        }
-        if (static_lds) nall = false;
+    KernelShape k = launch_shape(F, false, S, o);
+    if (k.s16) {
+        static const bool static_lds = any_static_lds({(const void*)trace_features<Cfg<F, true, true, true, false, false>>});
+        if (static_lds) k = without_stack16(k);
     }
-    if (o.slab32) {
-        if (o.lds_stack) launch_features_one<F, true, true>(L, stream, nall);
-        else launch_features_one<F, true, false>(L, stream, nall);
-    } else {
-        if (o.lds_stack) launch_features_one<F, false, true>(L, stream, nall);
-        else launch_features_one<F, false, false>(L, stream, nall);
-    }
+    const int bt = k.block_threads, wpb = bt / 64;
+    const size_t lds = launch_lds_bytes(k, S);
+    const unsigned nb = (unsigned)((L.n_blocks + wpb - 1) / wpb);
+    with_cfg<F, false, false>(k, [&](auto whole, auto part) {
+        const auto kernel = k.nall ? trace_features<decltype(whole)> : trace_features<decltype(part)>;
+        if (L.waves_per_simd) (void)blocks_per_cu(L, kernel, lds, bt);
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(bt), lds, stream, S, L.P, L.out);
+    });
     return hipGetLastError();
 }
 #define RT_FEATURES_DECL(F) \

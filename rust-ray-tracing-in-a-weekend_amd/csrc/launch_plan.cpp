@@ -17,20 +17,18 @@ constexpr int kMaxLdsStack = 48;
 // TLAS nodes kept in LDS (32 KB per block): the first kMaxLdsNodes in BFS order, i.e.
 // the top levels; deeper ones are read from L1/L2
 constexpr int kMaxLdsNodes = 512;
-// waves per SIMD of the final-scene variant (trace_device.hpp min_waves: its LDS budget is per
-// workgroup of the workgroups those waves make)
-#ifndef RT_MIN_WAVES_FINAL
-#define RT_MIN_WAVES_FINAL 4
-#endif
-// instance BLAS nodes staged in LDS at most (64 B each)
+// instance BLAS nodes staged in LDS at most
 #ifndef RT_LDS_BLAS_MAX
 #define RT_LDS_BLAS_MAX 1024   // the LDS budget decides (512-thread final variant: 512 of the final scene's then 548
                                // BLAS nodes, 110.95 -> 108.23 ms at C4 1920x1080x100, r03r_ab_c4.log; with 256-thread
                                // workgroups the budget held ~95: 64 staged 132.15 ms, 16 133.31, none 132.98, r03h)
 #endif
 constexpr int kMaxLdsBlas = RT_LDS_BLAS_MAX;
-// material (64 B) and texture (96 B) tables staged in LDS when both are this small (10 KB)
+// material and texture tables staged in LDS when both are this small (10 KB)
 constexpr int kMaxLdsMaterials = 64;
+// waves per CU the in-kernel reduction's ring is sized for (the launch clamps its grid to it): the
+// spheres variant's 6 per SIMD, f64 and f32 (RT_BLOCK_SPHERES, RT_BLOCK_F32_SPHERES); 5 elsewhere
+constexpr int kRingWavesSpheres = 24, kRingWavesOther = 20;
 
 }  // namespace
 
@@ -152,28 +150,28 @@ Plan plan(const SceneFacts& scene, const DeviceFacts& dev, const Options& opt, c
                        scene.n_materials > 0;
     pl.n_lds_materials = stage ? scene.n_materials : 0;
     pl.n_lds_textures = stage ? scene.n_textures : 0;
+    // the kernel shape this launches (launch_shapes.hpp): its workgroup, launch bound and LDS layout
+    const rtk::KernelShape& k = pl.shape = rtk::launch_shape(variant, pl.slab32 != 0, pl.lds_stack != 0, pl.f32 != 0, pl.n_lds_nodes,
+                                                             scene.n_tlas_nodes, scene.stack16_ok != 0);
+    const int bt = k.block_threads;
+    const size_t wg_waves = (size_t)(bt / 64), cu_waves = 4 * (size_t)k.min_waves;   // 4 SIMDs per CU
     // the top levels of the BFS-ordered instance BLAS in LDS too (variants with nested walks),
     // as many as the LDS left over at the block count the rest of the layout allows
     pl.n_lds_blas = 0;
     if (scene.n_blas_bfs > 0 && opt.lds_nodes && (variant & rtk::FEAT_INST_BLAS) != 0) {
-        const bool oct = pl.slab32 && pl.n_lds_nodes == scene.n_tlas_nodes && pl.n_lds_nodes > 0;
-        const int bt = rtk::block_threads_of(variant, pl.f32 != 0);   // workgroup threads (RT_BLOCK_FINAL)
-        const size_t base = (size_t)pl.n_lds_nodes * (oct ? 80 : 64) +
-                            (pl.lds_stack ? (size_t)scene.stack_entries * (size_t)bt * 4 : 0) +
-                            (size_t)pl.n_lds_materials * 64 + (size_t)pl.n_lds_textures * 96;
+        const size_t base = rtk::lds_layout(k, pl.n_lds_nodes, 0, scene.stack_entries, pl.n_lds_materials, pl.n_lds_textures).total;
         // the CU's 160 KB shared by `blocks` workgroups, each allocation rounded up to the LDS
         // granule (taken as 1 KB; the occupancy API does not round: a layout it rated at 3
         // blocks per CU ran 2 and took 174 instead of 133 ms, r03g_ab_c4.log), and no more
         // workgroups than the variant's registers allow (final scene 4 waves per SIMD, the
         // all-features variant 3: 16 or 12 waves per CU)
         const size_t lds_cu = dev.lds_per_cu, granule = 1024;
-        const size_t wave_blocks = std::max<size_t>(1, (size_t)(variant == rtk::FEAT_SET_FINAL ? 4 * RT_MIN_WAVES_FINAL : 12) /
-                                                           (size_t)(bt / 64));
+        const size_t wave_blocks = std::max<size_t>(1, cu_waves / wg_waves);
         const size_t blocks = std::max<size_t>(1, std::min(wave_blocks,
             lds_cu / (((std::max<size_t>(base, 1) + granule - 1) / granule) * granule)));
         const size_t budget = std::min(lds_cu / blocks, dev.lds_per_block) / granule * granule;
         const size_t spare = budget > base ? budget - base : 0;
-        pl.n_lds_blas = (int32_t)std::min<size_t>({(size_t)scene.n_blas_bfs, spare / 64, (size_t)kMaxLdsBlas});
+        pl.n_lds_blas = (int32_t)std::min<size_t>({(size_t)scene.n_blas_bfs, spare / rtk::kBvhNodeBytes, (size_t)kMaxLdsBlas});
     }
     // work blocks of one tile: 16-sample chunks, per-sample pool one chunk per block, item pool
     // two (C2 kernel ms, pool 1/2/4 chunks: 99.8/100.2/103.2; items 1/2/4: 106.8/104.1/105.0;
@@ -197,12 +195,10 @@ Plan plan(const SceneFacts& scene, const DeviceFacts& dev, const Options& opt, c
     }
     // the pool's in-kernel reduction needs blocks of exactly one chunk (a block's sum is the
     // chunk's) and batches on chunk boundaries; its ring: kPoolRing blocks for each wave of the
-    // persistent grid (at most 24 per CU: the spheres variant's 6 per SIMD, f64 and f32; the
-    // launch clamps its grid to ring_waves)
+    // persistent grid (kRingWaves* per CU)
     const bool ring_ok = retry.ring_allowed && opt.ring && pl.block_samples == chunk &&
                          chunk <= (int)(rtk::kRingSlot / 64) && rq.s_end <= (int)rtk::kRingSampleMask;
-    // (the spheres variant runs 6 waves per SIMD: RT_BLOCK_SPHERES, RT_BLOCK_F32_SPHERES)
-    const int ring_waves = dev.n_cus * (variant == rtk::FEAT_SET_SPHERES ? 24 : 20);
+    const int ring_waves = dev.n_cus * (variant == rtk::FEAT_SET_SPHERES ? kRingWavesSpheres : kRingWavesOther);
     const size_t ring_bytes = (size_t)ring_waves * rtk::kRingWaveDoubles * sizeof(double);
     // halved on an out-of-memory retry for this render only: the context's bound stays, so a
     // later render on it uses the memory freed since
@@ -249,16 +245,12 @@ Plan plan(const SceneFacts& scene, const DeviceFacts& dev, const Options& opt, c
     // per CU; each allocation rounded to the 1 KB granule as for the staged BLAS above). The random
     // scene: 22.2 KB of node records + 19.5 KB of stack + 24 KB = 66 KB, two 768-thread workgroups in
     // 160 KB as before; a scene whose stack leaves no room keeps the per-lane sample starts.
-    const bool s16 = variant == rtk::FEAT_SET_SPHERES &&
-                     rtk::stack16_launch(pl.slab32, pl.lds_stack, pl.n_lds_nodes, scene.n_tlas_nodes, scene.stack16_ok != 0);
-    if (RT_STAGE_SEEDS && s16 && !pl.f32 && pl.schedule == RT_SCHED_POOL) {
-        const int bt = rtk::block_threads_of(variant, false, true);
+    if (RT_STAGE_SEEDS && k.s16 && !pl.f32 && pl.schedule == RT_SCHED_POOL) {
         const size_t granule = 1024, stage = rtk::seed_stage_bytes_of(bt);
-        // (the slots start on a 32 B boundary: trace_device.hpp, lds_seeds_offset)
-        const size_t base = ((size_t)pl.n_lds_nodes * 80 + (size_t)scene.stack_entries * (size_t)bt * 2 + 31) / 32 * 32;
+        const size_t base = rtk::lds_seeds_offset(rtk::lds_layout(k, pl.n_lds_nodes, 0, scene.stack_entries, 0, 0).total);
         auto resident = [&](size_t bytes) {
             const size_t alloc = (std::max<size_t>(bytes, 1) + granule - 1) / granule * granule;
-            return alloc > dev.lds_per_block ? (size_t)0 : std::min<size_t>(std::max(1, 24 / (bt / 64)), dev.lds_per_cu / alloc);
+            return alloc > dev.lds_per_block ? (size_t)0 : std::min(std::max<size_t>(1, cu_waves / wg_waves), dev.lds_per_cu / alloc);
         };
         if (resident(base + stage) > 0 && resident(base + stage) == resident(base)) pl.seed_stage_bytes = stage;
     }
@@ -269,10 +261,7 @@ Plan plan(const SceneFacts& scene, const DeviceFacts& dev, const Options& opt, c
     // the spheres variant's 768 threads, the final scene's 1024 — takes a CU only when a whole
     // workgroup of its predecessor has left, and the two persistent grids then contend instead:
     // C5 4096x4096x4096 overlapped 11,471 ms per frame, in order 10,474, profiles/r06zz_c5_*)
-    const bool big_wg = rtk::block_threads_of(variant, pl.f32 != 0,
-                                              rtk::stack16_launch(pl.slab32, pl.lds_stack, pl.n_lds_nodes,
-                                                                  scene.n_tlas_nodes, scene.stack16_ok != 0)) > 256;
-    pl.overlap = opt.overlap && !big_wg && pl.batch < total && pl.schedule != RT_SCHED_CHUNKS;
+    pl.overlap = opt.overlap && bt <= 256 && pl.batch < total && pl.schedule != RT_SCHED_CHUNKS;
     if (pl.overlap) {
         fit = (long long)std::max<size_t>(1, out_cap / 2 / unit);
         pl.batch = std::min<long long>(total, pl.per_sample ? fit : fit * chunk);

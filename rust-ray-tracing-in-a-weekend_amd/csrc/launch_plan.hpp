@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "rt/rt_abi.h"
+#include "launch_shapes.hpp"
 #include "scene_lower.hpp"
 
 namespace rtp {
@@ -82,6 +83,7 @@ struct Plan {
     uint32_t variant = 0;       // rtk::variant_features of them
     int slab32 = 0, lds_stack = 0, f32 = 0;
     int schedule = 0;           // RT_SCHED_*, AUTO resolved
+    rtk::KernelShape shape{};   // the kernel instantiation those options and the staged TLAS launch (launch_shapes.hpp)
     // staged in LDS (SceneDev's fields of these names)
     int n_lds_nodes = 0, n_lds_materials = 0, n_lds_textures = 0, n_lds_blas = 0;
     // LDS bytes per workgroup of the wave-wide sample starts (SceneDev.seed_stage_bytes; launch_shapes.hpp

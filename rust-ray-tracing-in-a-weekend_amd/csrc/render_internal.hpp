@@ -34,6 +34,29 @@ struct Sink {
     int n_done = 0;
 };
 
+// What a plan launches: the scene's device view with the plan's staged counts, and the launch
+// options (timed: a count_work render sets o.count)
+struct PlannedLaunch {
+    rtk::SceneDev S;
+    rtk::LaunchOpts o;
+};
+inline PlannedLaunch planned_launch(const rtk::SceneDev& scene, const rtp::Plan& pl)
+{
+    PlannedLaunch l{scene, {}};
+    l.S.n_lds_nodes = pl.n_lds_nodes;
+    l.S.n_lds_materials = pl.n_lds_materials;
+    l.S.n_lds_textures = pl.n_lds_textures;
+    l.S.n_lds_blas = pl.n_lds_blas;
+    l.S.seed_stage_bytes = (int32_t)pl.seed_stage_bytes;
+    l.o.features = pl.features;
+    l.o.slab32 = pl.slab32;
+    l.o.lds_stack = pl.lds_stack;
+    l.o.count = 0;
+    l.o.pool = pl.schedule;
+    l.o.f32 = pl.f32;
+    return l;
+}
+
 // The launch params of a sample range, all but what the plan and the batch loop set (block sizes,
 // ring, sample range, work blocks). Fails on a context tile order that is not the frame's.
 int fill_kparams(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const Layout& lay, int chunk,

@@ -38,7 +38,6 @@ enum : uint32_t {
     // + Perlin and image textures, instances over spheres, media bounded by spheres (final scene)
     FEAT_SET_FINAL = FEAT_RECT | FEAT_INST | FEAT_MEDIUM | FEAT_NOISE | FEAT_IMAGE | FEAT_INST_BLAS
 };
-static_assert(FEAT_SET_FINAL == 287u, "block_threads_of");
 
 // the smallest compiled variant that holds a scene's features
 inline uint32_t variant_features(uint32_t scene_features)

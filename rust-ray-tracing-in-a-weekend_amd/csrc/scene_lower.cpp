@@ -8,6 +8,7 @@
 #include <unordered_map>
 
 #include "rt/rt_abi.h"
+#include "launch_shapes.hpp"   // kLdsNodeBytes
 #include "scene_features.hpp"
 
 namespace rtl {
@@ -391,11 +392,11 @@ int lower(const rt_scene_soa& s, bool hoist, Lowered& L, std::string& err)
     }
 
     if (hoist) hoist_root_leaf(s, L);
-    // Stack16 (trace_device.hpp): node records at LDS addresses < 32 KB (80 B each), BLAS node
+    // Stack16 (trace_device.hpp): node records (kLdsNodeBytes each) at LDS addresses < 32 KB, BLAS node
     // indices < 32768, and leaf codes ((first slot << 5) | count, stored complemented; BLAS slots
     // relative, above) strictly above the -32768 = ~32767 sentinel: every code < 32767 (a leaf
     // at first slot 1023 holding 31 primitives would complement to the sentinel itself)
-    L.stack16_ok = (L.n_tlas_nodes * (int64_t)80 <= 32767 - 80 && max_code < 32767 && s.n_nodes <= 32767) ? 1 : 0;
+    L.stack16_ok = (L.n_tlas_nodes * (int64_t)rtk::kLdsNodeBytes <= 32767 - (int64_t)rtk::kLdsNodeBytes && max_code < 32767 && s.n_nodes <= 32767) ? 1 : 0;
     // traversal stack: TLAS walk, then a nested BLAS walk (instances) above it, sized from the
     // depths validate measured (<= 32 each), each walk's bottom entry holding its RT_DONE
     // sentinel (traverse): the 66-entry scratch stack always fits

@@ -157,9 +157,10 @@ struct Cfg {
     static constexpr bool NALL = NALL_;
     static constexpr bool COUNT = COUNT_;
     static constexpr bool F32 = F32_;
-    // threads per workgroup (RT_BLOCK_FINAL): a property of the launched kernel, inherited by the
-    // reduced configurations of nested code (CfgDrop), which share its LDS stack
-    static constexpr int BT = block_threads_of(F_, F32_, RT_STACK16 && LDS_ && NALL_ && S32_);
+    // what the instantiation launches as (launch_shapes.hpp): a property of the launched kernel,
+    // inherited by the reduced configurations of nested code (CfgDrop), which share its LDS
+    static constexpr KernelShape SHAPE = kernel_shape(F_, S32_, LDS_, NALL_, F32_);
+    static_assert(SHAPE.s32 == S32_ && SHAPE.lds == LDS_ && SHAPE.nall == NALL_ && SHAPE.f32 == F32_, "the shape of this Cfg");
     using Real = typename std::conditional<F32_, float, double>::type;
     static constexpr bool STAGE = false;   // (CfgStage below)
 };
@@ -176,7 +177,7 @@ struct CfgStage : C {
 // clear), so e.g. the final scene's instanced BLAS of spheres compiles the sphere test only.
 // threads per workgroup (RT_BLOCK_FINAL; the LDS stack's lane stride)
 template <class C>
-constexpr int BlockThreads() { return C::BT; }
+constexpr int BlockThreads() { return C::SHAPE.block_threads; }
 
 template <class C, uint32_t DROP>
 struct CfgDrop : C {
@@ -232,25 +233,13 @@ struct Stack<false, false, BT> {
     int v[66];   // 32 + 32 entries + the two walks' RT_DONE sentinels
     __device__ __forceinline__ int& operator[](int i) { return v[i]; }
 };
-#ifndef RT_STACK16
-// 16-bit LDS stack entries in the spheres variant with the whole TLAS in LDS: its 35 KB of LDS
-// per block (22.7 KB of node records + a 12-entry 32-bit stack) let only 4 blocks share a CU's
-// 160 KB; with 6.1 KB of stack 5 blocks fit, and the variant runs at 5 waves per SIMD (96
-// VGPRs, min_waves) — C2 1200x800x100 16.48 -> 15.40 ms, same bits (profiles/r02ao_*)
-#define RT_STACK16 1
-#endif
 template <int BT>
 struct Stack16 {   // node records at LDS addresses < 32 KB, leaf codes > -32768 (SceneDev.stack16_ok)
     short* base;
     __device__ __forceinline__ short& operator[](int i) const { return base[i * BT]; }
 };
-// (the final-scene variant with 16-bit entries measured ~7 % slower: C4 1920x1080x100 142.1 vs
-// 132.7 ms, r03f_ab_c4.log; the spheres variant only)
 template <class C>
-constexpr bool Stack16Cfg()
-{
-    return RT_STACK16 && C::LDS && C::NALL && C::S32 && C::F == FEAT_SET_SPHERES;
-}
+constexpr bool Stack16Cfg() { return C::SHAPE.s16; }   // (launch_shapes.hpp, RT_STACK16)
 template <class C>
 using StackT = typename std::conditional<Stack16Cfg<C>(), Stack16<BlockThreads<C>()>,
                                          Stack<C::LDS, C::LDS && (C::F & FEAT_INST_BLAS) != 0, BlockThreads<C>()>>::type;
@@ -811,9 +800,10 @@ struct LdsNode {
     float ax[3][6];   // [axis][lo0 lo1 hi0 hi1 lo0 lo1]
     int32_t child[2];
 };
-static_assert(sizeof(LdsNode) == 80, "LdsNode layout");
+static_assert(sizeof(LdsNode) == kLdsNodeBytes && sizeof(rt_bvh_node) == kBvhNodeBytes, "staged node records");
+static_assert(sizeof(rt_material) == kMaterialBytes && sizeof(rt_texture) == kTextureBytes, "staged shading tables");
 template <class C>
-constexpr bool OctNodes() { return C::NALL && C::S32; }
+constexpr bool OctNodes() { return C::SHAPE.node_bytes == (int)sizeof(LdsNode); }
 // LDS byte address of a __shared__ object (the low 32 bits of its flat address), and an LDS
 // pointer from one: OctNodes node references are such addresses, so a node read needs no add
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)p; }
@@ -823,10 +813,7 @@ __device__ __forceinline__ const __attribute__((address_space(3))) T* lds_ptr(ui
     return (const __attribute__((address_space(3))) T*)(uintptr_t)a;
 }
 template <class C>
-constexpr int lds_node_bytes()
-{
-    return OctNodes<C>() ? (int)sizeof(LdsNode) : (int)sizeof(rt_bvh_node);
-}
+constexpr int lds_node_bytes() { return C::SHAPE.node_bytes; }
 __device__ __forceinline__ Node load_node_lds(uint32_t addr)
 {
     typedef unsigned u4v __attribute__((ext_vector_type(4)));
@@ -848,35 +835,16 @@ __device__ __forceinline__ Node load_node_lds(uint32_t addr)
 // global memory (the random scene's 485 materials would cost the spheres variant blocks per
 // CU). The flag is per launch, so the choice is wave-uniform.
 template <class C>
-constexpr bool StageShade() { return C::F != FEAT_SET_SPHERES; }
-// The block's dynamic LDS: [TLAS nodes][BLAS nodes][stack: entries x block lanes][materials][textures], one
-// layout for the kernel's offsets and the launcher's allocation (launch_one)
-struct LdsLayout {
-    size_t blas, stack, shade, total;   // byte offsets of the BLAS nodes, the stack and the material table; bytes
-};
-__host__ __device__ constexpr LdsLayout lds_layout(int n_nodes, int node_bytes, int n_blas, int stack_entries,
-                                                   int entry_bytes, int n_materials, int n_textures, int lanes)
-{
-    const size_t blas = (size_t)n_nodes * (size_t)node_bytes;
-    const size_t stack = blas + (size_t)n_blas * sizeof(rt_bvh_node);
-    const size_t shade = stack + (size_t)stack_entries * (size_t)lanes * (size_t)entry_bytes;
-    return LdsLayout{blas, stack, shade, shade + (size_t)n_materials * 64 + (size_t)n_textures * 96};
-}
-// The staged sample starts (RT_STAGE_SEEDS) follow that layout on a boundary of their slots' size
-// (kSeedSlotBytes): their byte offset from the layout's total. (A function of its own: the layout
-// function above is inlined by cost, and the kernels that do not stage keep their code.)
-__host__ __device__ constexpr size_t lds_seeds_offset(size_t layout_total) { return (layout_total + 31) / 32 * 32; }
+constexpr bool StageShade() { return C::SHAPE.stage_shade; }
 // the variants that stage BLAS nodes (SceneDev.n_lds_blas; the host sets it only for them)
-#ifndef RT_STAGE_BLAS
-#define RT_STAGE_BLAS 1
-#endif
 template <class C>
-constexpr bool StageBlas() { return RT_STAGE_BLAS && (C::F & FEAT_INST_BLAS) != 0; }
+constexpr bool StageBlas() { return C::SHAPE.stage_blas; }
+// The block's dynamic LDS (launch_shapes.hpp, lds_layout) of this configuration
 template <class C>
 __device__ __forceinline__ LdsLayout lds_layout_of(const SceneDev& S)
 {
     return lds_layout(S.n_lds_nodes, lds_node_bytes<C>(), StageBlas<C>() ? S.n_lds_blas : 0, C::LDS ? S.stack_entries : 0,
-                      Stack16Cfg<C>() ? 2 : 4, StageShade<C>() ? S.n_lds_materials : 0,
+                      C::SHAPE.entry_bytes, StageShade<C>() ? S.n_lds_materials : 0,
                       StageShade<C>() ? S.n_lds_textures : 0, BlockThreads<C>());
 }
 
@@ -1942,56 +1910,9 @@ __device__ __forceinline__ bool lane_work(const KParams& P, LaneWork& w)
     return true;
 }
 
-#ifndef RT_MIN_WAVES_F32_SPHERES
-#define RT_MIN_WAVES_F32_SPHERES 6   // 76 VGPRs (<= 80 for 6), 512-thread blocks (RT_BLOCK_F32_SPHERES)
-#endif
-#ifndef RT_MIN_WAVES_SPHERES
-#define RT_MIN_WAVES_SPHERES 1
-#endif
-// the f64 spheres variant with its 16-bit LDS stack (C1, C2, C5): 6 waves per SIMD at 80 VGPRs
-// (94 at 5, spill-free) with 768-thread workgroups (RT_BLOCK_SPHERES)
-#ifndef RT_MIN_WAVES_SPHERES_S16
-#define RT_MIN_WAVES_SPHERES_S16 6
-#endif
-#ifndef RT_MIN_WAVES_RECTINST
-// measured (Cornell 800x800x200): chunk schedule 4 waves 190 vs 202 ms; pool schedule 4: 80.7,
-// 3: 81.0; after the reciprocal divisions (more live state, 4 waves spilled to scratch):
-// 4: 66.6, 3: 58.6; round 2: without the nested BLAS walk (FEAT_INST_BLAS), the f64-slab
-// instantiation the node-free Cornell scenes run needs 125 VGPRs: 4 waves at this bound
-#define RT_MIN_WAVES_RECTINST 3
-#endif
-#ifndef RT_MIN_WAVES_ALL
-// measured, pool schedule: final scene 960x540x200 4: 112.0 ms (scratch spills: 0.7 TB of HBM
-// writes per launch), 3: 102.8, 2: 131.5; cornell smoke 600x600x200 4: 74.1, 3: 62.3, 2: 79.7
-#define RT_MIN_WAVES_ALL 3
-#endif
-#ifndef RT_MIN_WAVES_MEDIA
-#define RT_MIN_WAVES_MEDIA 3
-#endif
-#ifndef RT_MIN_WAVES_FINAL
-// round 3: 4 (127 VGPRs, no spills, once machine LICM no longer pins the cold paths' f64
-// constants in VGPRs and the hit record is dead during the walk); round 2 measured 3 best
-// (4: 112.0 ms with 0.7 TB of scratch writes per launch, 3: 102.8, 2: 131.5 at 960x540x200)
-#define RT_MIN_WAVES_FINAL 4
-#endif
-// the f32 final-scene variant: 4 like the f64 one (3 waves, 136-142 VGPRs and no spills even with
-// the small-sphere test, is slower: C4 1920x1080x100 f32 101.9 ms with 768-thread blocks, 107.0
-// with 256, against 89.4 at 4; profiles/r06s_ab_f32final_c4.log)
-#ifndef RT_MIN_WAVES_F32_FINAL
-#define RT_MIN_WAVES_F32_FINAL RT_MIN_WAVES_FINAL
-#endif
-// minimum waves per SIMD requested from the register allocator, per feature set
+// minimum waves per SIMD requested from the register allocator (launch_shapes.hpp, RT_MIN_WAVES_*)
 template <class C>
-constexpr int min_waves()
-{
-    return Stack16Cfg<C>() && C::F32 ? RT_MIN_WAVES_F32_SPHERES   // (the f32 mode's spheres variant)
-           : C::F32 && C::F == FEAT_SET_FINAL ? RT_MIN_WAVES_F32_FINAL
-           : Stack16Cfg<C>() && C::F == FEAT_SET_SPHERES ? RT_MIN_WAVES_SPHERES_S16
-           : C::F == FEAT_SET_SPHERES ? RT_MIN_WAVES_SPHERES
-           : C::F == FEAT_SET_RECTINST ? RT_MIN_WAVES_RECTINST
-           : C::F == FEAT_SET_MEDIA    ? RT_MIN_WAVES_MEDIA
-           : C::F == FEAT_SET_FINAL    ? RT_MIN_WAVES_FINAL : RT_MIN_WAVES_ALL;
-}
+constexpr int min_waves() { return C::SHAPE.min_waves; }
 
 // KParams comes by pointer: read where used (scalar loads) instead of pinning ~70 SGPRs
 // for the whole kernel (by value it spilled SGPRs into VGPR lanes).
@@ -2720,201 +2641,5 @@ __global__ void __launch_bounds__(BlockThreads<C>(), min_waves<C>()) trace_pool(
         }
     }
 }
-
-// ---------------------------------------------------------------------------
-// host-side launchers
-// ---------------------------------------------------------------------------
-struct Launch {
-    const SceneDev* S;
-    const KParams* P;
-    double* out;                   // chunk partials (chunk schedule) or per-sample radiance (pool)
-    unsigned long long* counters;
-    unsigned* work;                // pool / items: work-block counter
-    int pool;                      // 0 chunks, 1 per-sample pool, 2 item pool
-    unsigned long long n_blocks;   // 8x8 tiles x chunks
-    int* waves_per_simd;           // out (optional): resident blocks per CU = waves per SIMD (4-wave blocks)
-    unsigned max_waves = 0;        // per-sample pool with the in-kernel reduction: waves its ring holds
-};
-
-// Resident blocks per CU of a kernel (registers, LDS); waves per SIMD reported to the caller.
-template <class K>
-static int blocks_per_cu(const Launch& L, K kernel, size_t lds, int bt)
-{
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, bt, lds) != hipSuccess || per_cu <= 0) per_cu = 1;
-    if (L.waves_per_simd) *L.waves_per_simd = per_cu * (bt / 256);   // 4 SIMDs per CU
-    return per_cu;
-}
-
-// Persistent grid for the pool schedule: as many blocks as fit on the device at once.
-template <class K>
-static unsigned resident_blocks(const Launch& L, K kernel, size_t lds, int bt)
-{
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    return (unsigned)(cus * blocks_per_cu(L, kernel, lds, bt));
-}
-
-template <uint32_t F, bool S32, bool LDS, bool COUNT, bool F32>
-static void launch_one(const Launch& L, hipStream_t stream, bool nall)
-{
-    const SceneDev& S = *L.S;
-    const bool s16 = RT_STACK16 && LDS && nall && S32 && F == FEAT_SET_SPHERES;   // Stack16Cfg
-    const int node_bytes = nall && S32 ? (int)sizeof(LdsNode) : (int)sizeof(rt_bvh_node);   // lds_node_bytes
-    const bool stage = F != FEAT_SET_SPHERES;                   // StageShade
-    const bool blas = RT_STAGE_BLAS && (F & FEAT_INST_BLAS) != 0;   // StageBlas
-    const int bt = block_threads_of(F, F32, RT_STACK16 && LDS && nall && S32), wpb = bt / 64;   // BlockThreads
-    // wave-wide sample starts (RT_STAGE_SEEDS): the plan's bytes for this launch pick the per-sample
-    // pool's staged instantiation, which exists for the f64 16-bit-stack spheres kernels only
-    constexpr bool can_stage = RT_STAGE_SEEDS && RT_STACK16 && F == FEAT_SET_SPHERES && S32 && LDS && !F32;
-    const int seed_bytes = can_stage && nall && L.pool == 1 && S.seed_stage_bytes == (int)seed_stage_bytes_of(bt)
-                               ? S.seed_stage_bytes : 0;
-    const size_t lds_rest = lds_layout(S.n_lds_nodes, node_bytes, blas ? S.n_lds_blas : 0, LDS ? S.stack_entries : 0,
-                                       s16 ? 2 : 4, stage ? S.n_lds_materials : 0, stage ? S.n_lds_textures : 0, bt).total;
-    const size_t lds = seed_bytes ? lds_seeds_offset(lds_rest) + (size_t)seed_bytes : lds_rest;
-    if (L.pool) {
-        auto go = [&](auto kernel) {
-            unsigned nb = std::min<unsigned long long>(resident_blocks(L, kernel, lds, bt), (L.n_blocks + wpb - 1) / wpb);
-            if (L.max_waves) nb = std::max(1u, std::min(nb, L.max_waves / (unsigned)wpb));
-            hipLaunchKernelGGL(kernel, dim3(nb), dim3(bt), lds, stream, S, L.P, L.out, L.counters, L.work);
-        };
-        if constexpr (can_stage) {
-            if (seed_bytes) {
-                if (L.max_waves) go(trace_pool<CfgStage<Cfg<F, S32, LDS, true, COUNT, F32>>, false, true>);
-                else go(trace_pool<CfgStage<Cfg<F, S32, LDS, true, COUNT, F32>>, false>);
-                return;
-            }
-        }
-        if (L.pool == 2) {
-            if (nall) go(trace_pool<Cfg<F, S32, LDS, true, COUNT, F32>, true>);
-            else go(trace_pool<Cfg<F, S32, LDS, false, COUNT, F32>, true>);
-        } else if (L.max_waves) {   // the per-sample pool reducing in the kernel (KParams.ring)
-            if (nall) go(trace_pool<Cfg<F, S32, LDS, true, COUNT, F32>, false, true>);
-            else go(trace_pool<Cfg<F, S32, LDS, false, COUNT, F32>, false, true>);
-        } else {
-            if (nall) go(trace_pool<Cfg<F, S32, LDS, true, COUNT, F32>, false>);
-            else go(trace_pool<Cfg<F, S32, LDS, false, COUNT, F32>, false>);
-        }
-        return;
-    }
-    const unsigned nb = (unsigned)((L.n_blocks + wpb - 1) / wpb);
-    auto go = [&](auto kernel) {
-        if (L.waves_per_simd) (void)blocks_per_cu(L, kernel, lds, bt);
-        hipLaunchKernelGGL(kernel, dim3(nb), dim3(bt), lds, stream, S, L.P, L.out, L.counters);
-    };
-    if (nall) go(trace_chunks<Cfg<F, S32, LDS, true, COUNT, F32>>);
-    else go(trace_chunks<Cfg<F, S32, LDS, false, COUNT, F32>>);
-}
-
-// Variant table: feature set x slab precision x loop form. The launcher takes the
-// smallest feature set covering the scene.
-template <uint32_t F, bool COUNT>
-static void launch_f(const Launch& L, int slab32, int lds, hipStream_t stream)
-{
-    const SceneDev& S = *L.S;
-    bool nall = S.n_lds_nodes > 0 && S.n_lds_nodes == S.n_tlas_nodes;
-    // the whole-TLAS spheres instantiation keeps 16-bit stack entries (Stack16Cfg): a scene
-    // whose node addresses or leaf codes do not fit takes the partial-TLAS instantiation
-    // (the host's plan sizes overlap and LDS from the workgroup this ends in: launch_shapes.hpp
-    // stack16_launch states the same test in one expression; the two must agree)
-    constexpr bool S16F = F == FEAT_SET_SPHERES;   // Stack16Cfg's feature set
-    if (RT_STACK16 && S16F && slab32 && lds && !S.stack16_ok) nall = false;
-    // stack16_ok (scene_lower.cpp) assumes the node records start at LDS address 0, i.e. that rt_lds is
-    // the kernels' only __shared__ object: a static __shared__ variable would move the dynamic
-    // base up, and 16-bit stack entries would truncate node addresses past 32 KB. Checked on the
-    // compiled kernels: any static LDS in them sends the scene to the 32-bit-stack instantiation.
-    if (RT_STACK16 && S16F && slab32 && lds && nall) {
-        static int static_lds = -1;
-        if (static_lds < 0) {
-            static_lds = 0;
-            hipFuncAttributes a;
-            const void* ks[4] = {(const void*)trace_pool<Cfg<F, true, true, true, COUNT, false>, false>,
-                                 (const void*)trace_pool<Cfg<F, true, true, true, COUNT, false>, true>,
-                                 (const void*)trace_pool<Cfg<F, true, true, true, COUNT, false>, false, true>,
-                                 (const void*)trace_chunks<Cfg<F, true, true, true, COUNT, false>>};
-            for (const void* k : ks)
-                if (hipFuncGetAttributes(&a, k) != hipSuccess || a.sharedSizeBytes != 0) static_lds = 1;
-            if constexpr (RT_STAGE_SEEDS != 0 && RT_STACK16 != 0 && S16F) {   // the staged per-sample pool kernels (launch_one)
-                const void* kst[2] = {(const void*)trace_pool<CfgStage<Cfg<F, true, true, true, COUNT, false>>, false>,
-                                      (const void*)trace_pool<CfgStage<Cfg<F, true, true, true, COUNT, false>>, false, true>};
-                for (const void* k : kst)
-                    if (hipFuncGetAttributes(&a, k) != hipSuccess || a.sharedSizeBytes != 0) static_lds = 1;
-            }
-        }
-        if (static_lds) nall = false;
-    }
-    if (slab32) {
-        if (lds) launch_one<F, true, true, COUNT, false>(L, stream, nall);
-        else launch_one<F, true, false, COUNT, false>(L, stream, nall);
-    } else {
-        if (lds) launch_one<F, false, true, COUNT, false>(L, stream, nall);
-        else launch_one<F, false, false, COUNT, false>(L, stream, nall);
-    }
-}
-
-// One feature set's kernels, timed or counting (trace_v_*.hip instantiate one pair each,
-// one translation unit per pair).
-template <uint32_t F, bool COUNT>
-hipError_t launch_variant(const Launch& L, const LaunchOpts& o, hipStream_t stream)
-{
-    launch_f<F, COUNT>(L, o.slab32, o.lds_stack, stream);
-    return hipGetLastError();
-}
-
-// The f32 fast mode's kernels of one feature set (trace_f32_*.hip): f32 slab tests always
-// (an f32 path gains nothing from f64 boxes), no count variant.
-// The whole-TLAS spheres instantiation keeps 16-bit stack entries (Stack16Cfg), as launch_f's: a
-// scene whose node addresses or leaf codes do not fit takes the partial-TLAS instantiation.
-inline bool f32_nall(const SceneDev& S, uint32_t F, bool lds)
-{
-    const bool nall = S.n_lds_nodes > 0 && S.n_lds_nodes == S.n_tlas_nodes;
-    return nall && !(RT_STACK16 && F == FEAT_SET_SPHERES && lds && !S.stack16_ok);
-}
-template <uint32_t F>
-hipError_t launch_variant_f32(const Launch& L, const LaunchOpts& o, hipStream_t stream)
-{
-    const bool nall = f32_nall(*L.S, F, o.lds_stack);
-    if (o.lds_stack) launch_one<F, true, true, false, true>(L, stream, nall);
-    else launch_one<F, true, false, false, true>(L, stream, nall);
-    return hipGetLastError();
-}
-
-// The f32 mode's count_work variant (final scene and spheres: the f32-vs-f64 path-length and
-// step-cost comparison of DESIGN.md §5.6; trace_f32_*_count.hip)
-template <uint32_t F>
-hipError_t launch_variant_f32_count(const Launch& L, const LaunchOpts& o, hipStream_t stream)
-{
-    const bool nall = f32_nall(*L.S, F, o.lds_stack);
-    if (o.lds_stack) launch_one<F, true, true, true, true>(L, stream, nall);
-    else launch_one<F, true, false, true, true>(L, stream, nall);
-    return hipGetLastError();
-}
-#define RT_VARIANT_DECL(F, COUNT) \
-    extern template hipError_t launch_variant<F, COUNT>(const Launch&, const LaunchOpts&, hipStream_t);
-#define RT_VARIANT_F32_DECL(F) \
-    extern template hipError_t launch_variant_f32<F>(const Launch&, const LaunchOpts&, hipStream_t);
-RT_VARIANT_DECL(FEAT_SET_SPHERES, false)
-RT_VARIANT_DECL(FEAT_SET_SPHERES, true)
-RT_VARIANT_DECL(FEAT_SET_RECTINST, false)
-RT_VARIANT_DECL(FEAT_SET_RECTINST, true)
-RT_VARIANT_DECL(FEAT_SET_MEDIA, false)
-RT_VARIANT_DECL(FEAT_SET_MEDIA, true)
-RT_VARIANT_DECL(FEAT_SET_FINAL, false)
-RT_VARIANT_DECL(FEAT_SET_FINAL, true)
-RT_VARIANT_DECL(FEAT_ALL, false)
-RT_VARIANT_DECL(FEAT_ALL, true)
-RT_VARIANT_F32_DECL(FEAT_SET_SPHERES)
-RT_VARIANT_F32_DECL(FEAT_SET_RECTINST)
-RT_VARIANT_F32_DECL(FEAT_SET_MEDIA)
-RT_VARIANT_F32_DECL(FEAT_SET_FINAL)
-RT_VARIANT_F32_DECL(FEAT_ALL)
-extern template hipError_t launch_variant_f32_count<FEAT_SET_SPHERES>(const Launch&, const LaunchOpts&, hipStream_t);
-extern template hipError_t launch_variant_f32_count<FEAT_SET_FINAL>(const Launch&, const LaunchOpts&, hipStream_t);
-#undef RT_VARIANT_DECL
-#undef RT_VARIANT_F32_DECL
 
 }  // namespace rtk

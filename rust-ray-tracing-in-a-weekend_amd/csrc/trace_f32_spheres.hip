@@ -1,8 +1,8 @@
 // trace_f32_spheres.hip — instantiates the f32 fast mode of the megakernel (trace_device.hpp,
 // Cfg::F32) for one feature set (FEAT_SET_SPHERES); one translation unit per variant
 // so the build compiles them in parallel.
-#include "trace_device.hpp"
+#include "trace_launch.hpp"
 
 namespace rtk {
-template hipError_t launch_variant_f32<FEAT_SET_SPHERES>(const Launch&, const LaunchOpts&, hipStream_t);
+template hipError_t launch_variant<FEAT_SET_SPHERES, false, true>(const Launch&, const LaunchOpts&, hipStream_t);
 }  // namespace rtk

@@ -1,7 +1,7 @@
 // trace_kernel.hip — host-side dispatch of the megakernel (the variants live in
-// trace_v*.hip over trace_device.hpp), the per-pixel reductions of the schedules, and the
-// device numerics probe. See trace_device.hpp for the execution model.
-#include "trace_device.hpp"
+// trace_v*.hip over trace_device.hpp, their launcher in trace_launch.hpp), the per-pixel reductions
+// of the schedules, and the device numerics probe. See trace_device.hpp for the execution model.
+#include "trace_launch.hpp"
 
 namespace rtk {
 
@@ -283,6 +283,25 @@ __global__ void eval_numerics(int fn, const double* x, const double* y, const do
 // ---------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------
+// the variant of one kind (f64 or f32, timed or counting) that holds the feature set
+template <bool COUNT, bool F32>
+static hipError_t launch_kind(uint32_t f, const Launch& L, const LaunchOpts& o, hipStream_t stream)
+{
+    switch (f) {
+    case FEAT_SET_SPHERES: return launch_variant<FEAT_SET_SPHERES, COUNT, F32>(L, o, stream);
+    case FEAT_SET_FINAL: return launch_variant<FEAT_SET_FINAL, COUNT, F32>(L, o, stream);
+    }
+    if constexpr (COUNT && F32) {
+        return hipErrorNotSupported;   // count_work in the f32 mode: those two variants only
+    } else {
+        switch (f) {
+        case FEAT_SET_RECTINST: return launch_variant<FEAT_SET_RECTINST, COUNT, F32>(L, o, stream);
+        case FEAT_SET_MEDIA: return launch_variant<FEAT_SET_MEDIA, COUNT, F32>(L, o, stream);
+        default: return launch_variant<FEAT_ALL, COUNT, F32>(L, o, stream);
+        }
+    }
+}
+
 hipError_t launch_trace(const SceneDev& S, const KParams& Ph, const KParams* P, double* out,
                         unsigned long long* counters, unsigned* work, const LaunchOpts& o, hipStream_t stream)
 {
@@ -308,32 +327,9 @@ hipError_t launch_trace(const SceneDev& S, const KParams& Ph, const KParams* P, 
         if (e != hipSuccess) return e;
     }
     const uint32_t f = variant_features(o.features);
-    if (o.f32 && o.count) {
-        if (f == FEAT_SET_SPHERES) return launch_variant_f32_count<FEAT_SET_SPHERES>(L, o, stream);
-        if (f == FEAT_SET_FINAL) return launch_variant_f32_count<FEAT_SET_FINAL>(L, o, stream);
-        return hipErrorNotSupported;
-    }
-    if (o.f32) {
-        if (f == FEAT_SET_SPHERES) return launch_variant_f32<FEAT_SET_SPHERES>(L, o, stream);
-        if (f == FEAT_SET_RECTINST) return launch_variant_f32<FEAT_SET_RECTINST>(L, o, stream);
-        if (f == FEAT_SET_MEDIA) return launch_variant_f32<FEAT_SET_MEDIA>(L, o, stream);
-        if (f == FEAT_SET_FINAL) return launch_variant_f32<FEAT_SET_FINAL>(L, o, stream);
-        return launch_variant_f32<FEAT_ALL>(L, o, stream);
-    }
-    if (o.count) {
-        if (f == FEAT_SET_SPHERES) return launch_variant<FEAT_SET_SPHERES, true>(L, o, stream);
-        if (f == FEAT_SET_RECTINST) return launch_variant<FEAT_SET_RECTINST, true>(L, o, stream);
-        if (f == FEAT_SET_MEDIA) return launch_variant<FEAT_SET_MEDIA, true>(L, o, stream);
-        if (f == FEAT_SET_FINAL) return launch_variant<FEAT_SET_FINAL, true>(L, o, stream);
-        return launch_variant<FEAT_ALL, true>(L, o, stream);
-    }
-    if (f == FEAT_SET_SPHERES) return launch_variant<FEAT_SET_SPHERES, false>(L, o, stream);
-    if (f == FEAT_SET_RECTINST) return launch_variant<FEAT_SET_RECTINST, false>(L, o, stream);
-    if (f == FEAT_SET_MEDIA) return launch_variant<FEAT_SET_MEDIA, false>(L, o, stream);
-    if (f == FEAT_SET_FINAL) return launch_variant<FEAT_SET_FINAL, false>(L, o, stream);
-    return launch_variant<FEAT_ALL, false>(L, o, stream);
+    if (o.f32) return o.count ? launch_kind<true, true>(f, L, o, stream) : launch_kind<false, true>(f, L, o, stream);
+    return o.count ? launch_kind<true, false>(f, L, o, stream) : launch_kind<false, false>(f, L, o, stream);
 }
-
 
 hipError_t launch_reduce_samples(const double* samples, void* out, bool f64, SampleTiles g, int n_samples,
                                  int chunk, double scale, hipStream_t stream)

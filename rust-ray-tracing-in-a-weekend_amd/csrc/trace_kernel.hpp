@@ -5,7 +5,7 @@
 
 #include "rt/rt_scene.h"
 #include "scene_features.hpp"   // FEAT_*, variant_features, RT_DEFER_INST
-#include "launch_shapes.hpp"    // RT_BLOCK_*, block_threads_of, the ring's constants, tiled_pixels
+#include "launch_shapes.hpp"    // KernelShape, lds_layout, RT_BLOCK_*, block_threads_of, the ring's constants, tiled_pixels
 
 namespace rtk {
 

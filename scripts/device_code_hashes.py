@@ -6,8 +6,11 @@
 For every object of either build directory that carries a gfx950 code object with a .text section
 (extracted as scripts/kernel_regs.py does), the sha256 (16 hex) of its .text, .rodata and .note
 sections. Sections, not whole files: a code object's symbol table carries the source path, so two
-checkouts of identical source differ as files. Exit status 1 if a kernel object is missing from one
-build or any section differs.
+checkouts of identical source differ as files. For the same reason a kernel descriptor's code
+entry (in .rodata, relative to the descriptor itself) is hashed as an offset into .text: the
+translation unit's id symbol (__hip_cuid_<hex>, a hash of the source path, printed without leading
+zeros) sits in .dynstr before .rodata, and a name one character shorter moves every descriptor by
+an alignment step. Exit status 1 if a kernel object is missing from one build or any section differs.
 """
 import hashlib
 import os
@@ -21,6 +24,24 @@ from kernel_regs import LLVM, code_objects  # noqa: E402
 SECTIONS = (".text", ".rodata", ".note")
 
 
+def rebase_code_entries(co: str, rodata: bytes) -> bytes:
+    """.rodata with each kernel descriptor's kernel_code_entry_byte_offset (8 bytes at +16, relative
+    to the descriptor) replaced by the entry's offset in .text."""
+    vma = {}
+    for line in subprocess.run([f"{LLVM}/llvm-objdump", "-h", co], capture_output=True, text=True).stdout.splitlines():
+        f = line.split()
+        if len(f) >= 4 and f[1] in (".rodata", ".text"):
+            vma[f[1]] = int(f[3], 16)
+    out = bytearray(rodata)
+    for line in subprocess.run([f"{LLVM}/llvm-objdump", "-t", co], capture_output=True, text=True).stdout.splitlines():
+        f = line.split()
+        if len(f) >= 5 and f[-1].endswith(".kd") and ".rodata" in f:
+            at = int(f[0], 16) - vma[".rodata"] + 16
+            entry = int(f[0], 16) + int.from_bytes(out[at:at + 8], "little", signed=True) - vma[".text"]
+            out[at:at + 8] = entry.to_bytes(8, "little", signed=True)
+    return bytes(out)
+
+
 def section_hashes(co: str, tmp: str) -> dict:
     out = {}
     for sec in SECTIONS:
@@ -30,6 +51,8 @@ def section_hashes(co: str, tmp: str) -> dict:
         subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section={sec}={dump}", co, os.path.join(tmp, "y.o")],
                        capture_output=True)
         data = open(dump, "rb").read() if os.path.exists(dump) else b""
+        if sec == ".rodata" and data:
+            data = rebase_code_entries(co, data)
         out[sec] = f"{hashlib.sha256(data).hexdigest()[:16]} ({len(data)} B)" if data else "-"
     return out
 

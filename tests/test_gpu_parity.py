@@ -268,6 +268,37 @@ def test_cornell_variant_occupancy(rt, renderer):
         assert st.slab32 == (0 if scene_id == 5 else 1)
 
 
+@pytest.mark.parametrize("scene_id", [0, 5, 7])
+def test_every_variant_tuple_launches_the_default_bits(rt, scene_id):
+    """Every rt_ctx_set_variant tuple (slab32 x lds_stack x lds_nodes: each a different kernel shape,
+    csrc/launch_shapes.hpp) under every schedule — chunks, the per-sample pool with its buffer and
+    with its ring, the item pool — renders the default tuple's bits, and so does the features pass.
+    At test_cornell_variant_occupancy's size, which asserts the default tuple's waves per SIMD."""
+    world = rt.World(1).build_scene(scene_id)
+    cam, bg = rt.scene_camera(scene_id, 16, 16)
+    params = lambda: rt.Renderer.params(16, 16, 2, 50, bg, 1, out_format=rt.RT_OUT_F64)
+    r = rt.Renderer(0)
+    try:
+        r.upload(world)
+        ref = r.render(cam, params())
+        ref_features = r.render_features(cam, params())
+        for v in [(a, b, c) for a in (1, 0) for b in (1, 0) for c in (1, 0)]:
+            r.set_variant(*v)
+            for sched, ring in ((rt.RT_SCHED_CHUNKS, 1), (rt.RT_SCHED_POOL, 0), (rt.RT_SCHED_POOL, 2), (rt.RT_SCHED_ITEMS, 1)):
+                r.set_schedule(sched)
+                r.set_option(rt.RT_OPT_POOL_RING, ring)
+                assert np.array_equal(r.render(cam, params()), ref), (scene_id, v, sched, ring)
+                st = r.stats()
+                assert (st.schedule, st.ring_bytes > 0) == (sched, ring == 2), (scene_id, v, sched, ring)
+                # (the Cornell box has no BVH node: no slab test, nothing of a TLAS to stage)
+                nodes = scene_id != 5
+                assert (st.slab32, st.lds_stack, st.lds_nodes > 0) == (v[0] and nodes, v[1], v[2] == 1 and nodes), (scene_id, v)
+            for got, want in zip(r.render_features(cam, params()), ref_features):
+                assert np.array_equal(got, want), (scene_id, v)
+    finally:
+        r.close()
+
+
 def _golden_cases():
     from tests.golden import make_golden as mg
     return mg.CASES, mg.key
