@@ -35,6 +35,10 @@
  *   rt_denoise_guided         (new) rt_denoise with those buffers in its weights
  *   rt_denoise_atrous         (new) a second post-filter: an edge-stopping a-trous wavelet over the
  *                             same inputs, which also hands back the noise left in its result
+ *   rt_render_adaptive_halves (new) rt_render_adaptive that also hands back the means of the even and
+ *                             of the odd samples
+ *   rt_denoise_cross          (new) rt_denoise over two half frames, each filtered with the other's
+ *                             weights, with the error left read off their difference
  *
  * Threading: a context is bound to one device and is used by one host thread at
  * a time. Worlds are plain host objects.
@@ -492,6 +496,30 @@ typedef struct rt_adaptive_stats {
 } rt_adaptive_stats;
 int rt_adaptive_last_stats(rt_ctx* ctx, rt_adaptive_stats* out);
 
+/* The adaptive frame plus its two half frames (additive to ABI v6: new symbols only), the input of
+ * rt_denoise_cross. Everything rt_render_adaptive does, bit for bit: the same passes and stop
+ * decisions, the same mean, tile_spp, tile_error and stderr_map, the same rt_adaptive_last_stats and
+ * rt_last_stats conventions, the same errors (RT_PREC_F32 contexts: RT_ERR_UNSUPPORTED; one GPU,
+ * whole frames); and halves NULL, either member NULL, or mean_a, mean_b and out->mean not three
+ * different buffers: RT_ERR_INVALID.
+ * The split. Half A holds the samples with an even global sample index s (the s of the (pixel, s)
+ * key every draw has), half B the odd ones. A tile that stopped at n samples has n_a = (n + 1) / 2
+ * and n_b = n / 2 of them.
+ * The sums. S_a is summed as S is, restricted to its parity: per chunk, a half-sum starts from 0.0
+ * and adds the chunk's samples of that parity in sample order; the chunk half-sums are added in
+ * chunk order to 0.0. S_b likewise. mean_a = S_a * (1 / n_a), mean_b = S_b * (1 / n_b), in
+ * p->out_format, height x width x 3, row 0 = bottom; device pointers iff p->out_on_device.
+ * The bits do not depend on buffer batches (RT_OPT_TRACE_BUF_BYTES): the open chunk of each half is
+ * carried across batches as S's is. At spp = min_spp = 2 mean_a is rt_render's frame at spp = 1.
+ * The moments kernel's second instantiation carries the six half accumulators beside S and Q;
+ * rt_render_adaptive keeps launching the first. */
+typedef struct rt_adaptive_halves {
+    void* mean_a;   /* required: the mean of the even samples */
+    void* mean_b;   /* required: the mean of the odd samples */
+} rt_adaptive_halves;
+int rt_render_adaptive_halves(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p,
+                              const rt_adaptive_params* ap, const rt_adaptive_out* out, const rt_adaptive_halves* halves);
+
 /* The criterion above on the host, no device needed: sums (height x width x 3) and q (height x
  * width) are a frame's S and Q, tile_spp its per-tile sample counts (every one >= 2, else
  * RT_ERR_INVALID); writes E_t per raster tile to tile_error_out and se per pixel to stderr_out
@@ -696,6 +724,85 @@ typedef struct rt_atrous_stats {
     int64_t scratch_bytes;  /* state scratch that call used: 0, 1 or 2 x (32 width height) */
 } rt_atrous_stats;
 int rt_atrous_last_stats(rt_ctx* ctx, rt_atrous_stats* out);
+
+/* ---- cross-filtered NL-means over two half frames (additive to ABI v6: new symbols only) ---------
+ * rt_denoise's weights are computed from the very pixels they then average, so the noise of a weight
+ * and the noise of the pixel it multiplies are correlated, and no output says how much error is
+ * left. The dual-buffer answer of Rousselle, Knaus, Zwicker 2012: the pixel's samples are split into
+ * two independent halves, each half is filtered with the weights taken from the other, the two
+ * results are averaged, and the error left is read off their difference.
+ *
+ * Inputs: M_A and M_B, height x width x 3 mean radiance of the two halves (f32 or f64, row 0 =
+ * bottom; e.g. the means over a pixel's even and over its odd samples); se, height x width f64, the
+ * standard error of the whole mean (rt_adaptive_out.stderr_map); optional guides g
+ * (rt_denoise_guides with rt_denoise_guided's meaning; NULL or all three frames NULL: no feature
+ * term); radius r in 1..10; patch f in 0..3; k > 0 and finite; variance_scale > 0 and finite. All
+ * arithmetic is f64 with no contraction and no fast math; f32 input is widened first.
+ *   Y_h(a) = the luminance of M_h(a), h in {A, B}, by rt_render_adaptive's expression for Y
+ *   V(a)   = variance_scale (se(a) se(a)): the variance of one half's luminance. A half of n / 2
+ *            samples has twice the whole mean's variance, so halves of equal size take 2.0
+ * A pixel a is bad if Y_A(a), Y_B(a) or V(a) is not finite; both Y_A and Y_B of a bad pixel count as
+ * NaN, so no pair that touches it has a weight.
+ *   delta_h(a, o), D_h(p, o): exactly rt_denoise's delta and D, from Y_h and V: the same valid-pair
+ *            rule, the same division by the number of valid s, direct patch sums in the same order
+ *   Phi(p, o): exactly rt_denoise_guided's feature term, the same for both halves; skipped without
+ *            guides
+ *   w_h(p, o) = exp(-(max(0, D_h(p, o)) + Phi(p, o))) if both are finite, otherwise 0;
+ *            w_h(p, (0,0)) = 1
+ * Cross application, over the offsets with p + o inside the image in raster order (dy outer, dx
+ * inner), terms with w = 0 skipped, not multiplied:
+ *   F_A(p) = sum_o w_B(p, o) M_A(p + o) / sum_o w_B(p, o)
+ *   F_B(p) = sum_o w_A(p, o) M_B(p + o) / sum_o w_A(p, o)
+ * A bad pixel keeps F_A(p) = M_A(p) and F_B(p) = M_B(p).
+ *   out(p) = 0.5 (F_A(p) + F_B(p)) per channel
+ * out has the means' format; an f32 out is the f64 result rounded once. The optional stderr_out
+ * (height x width f64):
+ *   e(p)  = 0.5 (Y(F_A(p)) - Y(F_B(p))),  E2(p) = e(p) e(p), from the unrounded F
+ *   stderr_out(p) = sqrt of the 3 x 3 binomial mean of E2 around p by rt_denoise_atrous's Vbar rule:
+ *           weights (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4), over the neighbours inside the image whose E2
+ *           is finite, divided by the sum of the weights taken, in raster order (dy outer, dx inner).
+ *           Where E2(p) itself is not finite, stderr_out(p) = sqrt(E2(p)).
+ * What stderr_out is: the standard error of out's luminance as far as the two halves disagree.
+ * (F_A - F_B) / 2 has the variance of (F_A + F_B) / 2 when the halves are independent, and one
+ * squared draw of it per pixel is smoothed over 3 x 3. That is out's variance, not its bias: both
+ * halves share the blur of the filter, and it cancels in their difference. Where the filter
+ * over-blurs, stderr_out understates the error.
+ * With M_A = M_B = M and variance_scale = 1 the filter is rt_denoise (with guides rt_denoise_guided)
+ * bit for bit on a frame whose se is finite everywhere (rt_denoise gives a pair whose far end has
+ * se = Inf a delta of 0, the bad-pixel rule here gives it none), and stderr_out is 0. Swapping the halves changes no bit of out
+ * or stderr_out. Nothing depends on the device's tiling: the result repeats bit for bit, and the
+ * device and host filters differ only by their exp. */
+typedef struct rt_cross_params {
+    int32_t width, height, format, on_device;  /* as rt_denoise_params */
+    int32_t radius, patch;
+    double k;
+    double variance_scale;   /* 2.0 for the two halves of an evenly split mean */
+    void* stream;            /* hipStream_t (NULL = the context's stream) */
+} rt_cross_params;
+/* RT_ERR_INVALID as rt_denoise_guided returns it, and for a null mean_a or mean_b, out equal to one
+ * of the inputs, stderr_out equal to stderr_map or to another frame of the call, variance_scale not
+ * greater than 0 and finite. mean_a == mean_b is allowed. Needs no uploaded scene. Every pointer is a
+ * device pointer iff p->on_device; with it set the call is only enqueued, like rt_denoise. With
+ * stderr_out the kernel's e(p) goes through a height x width f64 scratch the context owns, allocated
+ * on first need and grown when a larger frame arrives (a call that grows it may wait for the
+ * stream), and a second small kernel takes the 3 x 3 rule; without it there is one launch and no
+ * scratch. */
+int rt_denoise_cross(rt_ctx* ctx, const rt_cross_params* p, const void* mean_a, const void* mean_b,
+                     const double* stderr_map, const rt_denoise_guides* g /* may be NULL */, void* out,
+                     double* stderr_out /* may be NULL */);
+/* The same filter on the host, no device needed (on_device and stream are ignored). */
+int rt_denoise_cross_host(const rt_cross_params* p, const void* mean_a, const void* mean_b, const double* stderr_map,
+                          const rt_denoise_guides* g /* may be NULL */, void* out, double* stderr_out /* may be NULL */);
+
+typedef struct rt_cross_stats {
+    double kernel_ms;        /* last rt_denoise_cross: its one or two kernels (HIP events; waits if only enqueued) */
+    int32_t radius, patch;
+    int32_t lds_bytes;       /* LDS of one workgroup of the filter kernel: (3 SW^2 + 4 PW PS) 8 bytes, SW = 16 +
+                                2 (radius + patch), PW = 16 + 2 patch, PS = 16 if patch == 0, else 48 */
+    int32_t reserved0;
+    int64_t scratch_bytes;   /* e scratch that call used: 0 without stderr_out, else 8 width height */
+} rt_cross_stats;
+int rt_cross_last_stats(rt_ctx* ctx, rt_cross_stats* out);
 
 /* ---- output ------------------------------------------------------------------------------ */
 /* P3 PPM byte for byte as the reference writes it (write_color, math.rs:119-132; main.rs:472,

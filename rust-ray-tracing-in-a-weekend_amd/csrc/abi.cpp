@@ -104,6 +104,7 @@ int rt_ctx_create(int device, rt_ctx** out)
     if (e == hipSuccess) e = c->ev_dn.create();
     if (e == hipSuccess) e = c->ev_ft.create();
     if (e == hipSuccess) e = c->ev_at.create();
+    if (e == hipSuccess) e = c->ev_x.create();
     if (e == hipSuccess) e = c->ev_done.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_in.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_tr.create(hipEventDisableTiming);
@@ -496,7 +497,7 @@ int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_
         if (sink.moments) {
             HIP_TRY(rtk::launch_adaptive_moments(buf, *sink.moments, K.tiles_x, b1 - b0, chunk,
                                                  (int)(((long long)b0 - s_begin) % chunk), bi == pl.n_batches - 1,
-                                                 sink.n_done, stream));
+                                                 sink.n_done, stream, sink.halves, b0));
         } else if (!pl.per_sample) {
             if (acc) HIP_TRY(rtk::launch_accumulate(buf, acc, n_px, K.n_chunks, stream));
             else HIP_TRY(rtk::launch_reduce(buf, sink.out, sink.f64, n_px, K.n_chunks, sink.scale, stream));

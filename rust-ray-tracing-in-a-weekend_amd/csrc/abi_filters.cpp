@@ -1,13 +1,15 @@
-// abi_filters.cpp — the two post-filters behind the C ABI (include/rt/rt_abi.h): the variance-guided
-// NL-means filter (rt_denoise, rt_denoise_guided; denoise_kernel.hip) and the variance-guided
-// a-trous wavelet filter (rt_denoise_atrous; atrous_kernel.hip), with their stats. Their host
-// counterparts are denoise_host.cpp and atrous_host.cpp.
+// abi_filters.cpp — the post-filters behind the C ABI (include/rt/rt_abi.h): the variance-guided
+// NL-means filter (rt_denoise, rt_denoise_guided; denoise_kernel.hip), the variance-guided
+// a-trous wavelet filter (rt_denoise_atrous; atrous_kernel.hip) and the cross-filtered NL-means over
+// two half frames (rt_denoise_cross; cross_kernel.hip), with their stats. Their host counterparts
+// are denoise_host.cpp, atrous_host.cpp and cross_host.cpp.
 #include <hip/hip_runtime.h>
 
 #include <initializer_list>
 
 #include "rt/rt_abi.h"
 #include "atrous.hpp"
+#include "cross.hpp"
 #include "ctx_internal.hpp"
 #include "denoise.hpp"
 #include "filter_guides.hpp"
@@ -202,6 +204,76 @@ int rt_atrous_last_stats(rt_ctx* c, rt_atrous_stats* out)
         c->wstats.kernel_ms = ms[0];
     }
     *out = c->wstats;
+    return RT_OK;
+}
+
+// ---- cross-filtered NL-means over two half frames (rt_abi.h: the filter; cross_kernel.hip; cross_host.cpp)
+int rt_denoise_cross(rt_ctx* c, const rt_cross_params* p, const void* mean_a, const void* mean_b,
+                     const double* stderr_map, const rt_denoise_guides* g, void* out, double* stderr_out)
+{
+    if (!c) return fail(RT_ERR_INVALID, "null argument");
+    if (const char* bad = rtk::cross_check(p, mean_a, mean_b, stderr_map, out, stderr_out)) return fail(RT_ERR_INVALID, bad);
+    rtk::DenoiseGuides G;
+    if (const char* bad = rtk::guides_check(g, G)) return fail(RT_ERR_INVALID, bad);
+    const bool f64 = p->format == RT_OUT_F64, on_dev = p->on_device != 0;
+    const size_t hw = (size_t)p->width * (size_t)p->height;
+    const size_t b1 = hw * sizeof(double), b3 = 3 * b1, frame_bytes = hw * 3 * (f64 ? 8 : 4);
+    const size_t scratch_bytes = stderr_out ? b1 : 0;
+
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = p->stream ? (hipStream_t)p->stream : c->stream;
+    StreamScope scope(c, stream);
+    int rc = scope.begin();
+    if (rc) return rc;
+    // the context's e scratch, grown on demand (a call without stderr_out needs none)
+    rc = c->cross_buf.reserve(stream, scratch_bytes);
+    if (rc) return rc;
+    double* const e = scratch_bytes ? c->cross_buf.as<double>() : nullptr;
+
+    HostStage st;
+    if (!on_dev) {
+        rc = st.stage(stream, {{mean_a, frame_bytes, false}, {mean_b, frame_bytes, false}, {stderr_map, b1, false},
+                               {out, frame_bytes, true}, {stderr_out, b1, true}, {G.albedo, b3, false},
+                               {G.normal, b3, false}, {G.depth, b1, false}});
+        if (rc) return rc;
+        mean_a = st.dev(0);
+        mean_b = st.dev(1);
+        stderr_map = (const double*)st.dev(2);
+        out = st.dev(3);
+        stderr_out = (double*)st.dev(4);
+        G.albedo = (const double*)st.dev(5);
+        G.normal = (const double*)st.dev(6);
+        G.depth = (const double*)st.dev(7);
+    }
+    HIP_TRY(c->ev_x.record(0, stream));
+    HIP_TRY(rtk::launch_cross(mean_a, mean_b, stderr_map, out, stderr_out, e, f64, p->width, p->height, p->radius,
+                              p->patch, p->k, p->variance_scale, G, stream));
+    HIP_TRY(c->ev_x.record(1, stream));
+    c->xstats = rt_cross_stats{};
+    c->xstats.radius = p->radius;
+    c->xstats.patch = p->patch;
+    c->xstats.lds_bytes = rtk::cross_lds_bytes(p->radius, p->patch);
+    c->xstats.scratch_bytes = (int64_t)scratch_bytes;
+    c->ev_x.arm();
+    rc = st.copy_back(stream);
+    if (rc) return rc;
+    rc = scope.end();
+    if (rc) return rc;
+    if (!on_dev) HIP_TRY(hipStreamSynchronize(stream));   // (the block is freed once its copies are done)
+    return RT_OK;
+}
+
+int rt_cross_last_stats(rt_ctx* c, rt_cross_stats* out)
+{
+    if (!c || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (c->ev_x.pending) {
+        HIP_TRY(hipSetDevice(c->device));
+        float ms[1] = {0};
+        const int rc = c->ev_x.resolve(ms);
+        if (rc) return rc;
+        c->xstats.kernel_ms = ms[0];
+    }
+    *out = c->xstats;
     return RT_OK;
 }
 

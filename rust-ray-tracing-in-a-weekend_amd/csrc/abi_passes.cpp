@@ -45,8 +45,12 @@ int rt_adaptive_tile_errors_host(const double* sums, const double* q, const uint
     return RT_OK;
 }
 
-int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_adaptive_params* ap,
-                       const rt_adaptive_out* out)
+}  // extern "C"
+
+// rt_render_adaptive (hv null) and rt_render_adaptive_halves: one driver, the second with the two
+// half sums carried beside the frame's moments and resolved after them
+static int render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_adaptive_params* ap,
+                           const rt_adaptive_out* out, const rt_adaptive_halves* hv)
 {
     if (!c || !cam || !p || !ap || !out || !out->mean) return fail(RT_ERR_INVALID, "null argument");
     if (!c->has_scene) return fail(RT_ERR_NO_SCENE, "no scene uploaded");
@@ -79,11 +83,13 @@ int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
     int rc = scope.begin();
     if (rc) return rc;
 
-    // device state: [sum | sum_open | q | q_open | tile_error | se map (host-bound only)] f64, then
+    // device state: [sum | sum_open | q | q_open | tile_error | se map (host-bound only) | halves:
+    // sum_a | sum_a_open | sum_b | sum_b_open | the two half means (host-bound only)] f64, then
     // [tile_spp | order A | order B | counts] u32; zeroed: the sums start from 0.0
     const size_t hw = (size_t)W * (size_t)H, nt = (size_t)n_tiles;
     const bool own_se = out->stderr_map && !on_dev;
-    const size_t n_f64 = 8 * hw + nt + (own_se ? hw : 0), n_u32 = 3 * nt + 2;
+    const size_t n_base = 8 * hw + nt + (own_se ? hw : 0);
+    const size_t n_f64 = n_base + (hv ? 12 * hw + (on_dev ? 0 : 6 * hw) : 0), n_u32 = 3 * nt + 2;
     DevBuf blk;   // (of the call's own: freed on every way out)
     HIP_TRY(blk.alloc(n_f64 * sizeof(double) + n_u32 * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(blk.p, 0, n_f64 * sizeof(double) + n_u32 * sizeof(uint32_t), stream));
@@ -102,6 +108,13 @@ int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
     F.width = W;
     F.height = H;
     F.tiles_x = tiles_x;
+    rtk::AdaptiveHalves Hf{};
+    if (hv) {
+        Hf.sum_a = d + n_base;
+        Hf.sum_a_open = d + n_base + 3 * hw;
+        Hf.sum_b = d + n_base + 6 * hw;
+        Hf.sum_b_open = d + n_base + 9 * hw;
+    }
     {
         std::vector<uint32_t> raster(nt);
         for (size_t i = 0; i < nt; ++i) raster[i] = (uint32_t)i;
@@ -126,6 +139,7 @@ int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
         Sink sink;
         sink.moments = &F;
         sink.n_done = end;
+        sink.halves = hv ? &Hf : nullptr;
         rc = run_range(c, cam, &rp, done, end, chunk, stream, sink);
         if (rc) return rc;
         HIP_TRY(ev.record(0, stream));
@@ -166,6 +180,16 @@ int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
     if (own_se) HIP_TRY(hipMemcpyAsync(out->stderr_map, se_dev, hw * sizeof(double), kind, stream));
     if (out->tile_spp) HIP_TRY(hipMemcpyAsync(out->tile_spp, F.tile_spp, nt * sizeof(uint32_t), kind, stream));
     if (out->tile_error) HIP_TRY(hipMemcpyAsync(out->tile_error, F.tile_error, nt * sizeof(double), kind, stream));
+    if (hv) {
+        void* dev_a = on_dev ? hv->mean_a : (void*)(d + n_base + 12 * hw);
+        void* dev_b = on_dev ? hv->mean_b : (void*)(d + n_base + 15 * hw);
+        HIP_TRY(rtk::launch_adaptive_resolve_halves(Hf.sum_a, Hf.sum_b, F.tile_spp, dev_a, dev_b,
+                                                    p->out_format == RT_OUT_F64, W, H, stream));
+        if (!on_dev) {
+            HIP_TRY(hipMemcpyAsync(hv->mean_a, dev_a, mean_bytes, kind, stream));
+            HIP_TRY(hipMemcpyAsync(hv->mean_b, dev_b, mean_bytes, kind, stream));
+        }
+    }
     rc = scope.end();
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(stream));
@@ -182,6 +206,23 @@ int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
     c->pending_counts = false;
     c->astats = as;
     return RT_OK;
+}
+
+extern "C" {
+
+int rt_render_adaptive(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_adaptive_params* ap,
+                       const rt_adaptive_out* out)
+{
+    return render_adaptive(c, cam, p, ap, out, nullptr);
+}
+
+int rt_render_adaptive_halves(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rt_adaptive_params* ap,
+                              const rt_adaptive_out* out, const rt_adaptive_halves* halves)
+{
+    if (!halves || !halves->mean_a || !halves->mean_b) return fail(RT_ERR_INVALID, "null argument");
+    if (halves->mean_a == halves->mean_b || (out && (halves->mean_a == out->mean || halves->mean_b == out->mean)))
+        return fail(RT_ERR_INVALID, "rt_adaptive_halves: mean_a, mean_b and the mean must be three buffers");
+    return render_adaptive(c, cam, p, ap, out, halves);
 }
 
 int rt_adaptive_last_stats(rt_ctx* c, rt_adaptive_stats* out)

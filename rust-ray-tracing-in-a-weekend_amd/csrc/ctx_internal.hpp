@@ -164,6 +164,9 @@ struct rt_ctx {
     rt_atrous_stats wstats{};           // the last rt_denoise_atrous (rt_atrous_last_stats)
     EventSpan<2> ev_at;                 //   around its level kernels
     DevBuf atrous_buf;                  //   its state scratch between levels (rtk::AtrousRec)
+    rt_cross_stats xstats{};            // the last rt_denoise_cross (rt_cross_last_stats)
+    EventSpan<2> ev_x;                  //   around its kernels
+    DevBuf cross_buf;                   //   e(p) between its two kernels (f64 per pixel; only with stderr_out)
     // what a render's launch plan is made from (launch_plan.hpp): the uploaded scene, the device, the switches
     rtp::SceneFacts scene;
     rtp::DeviceFacts dev;

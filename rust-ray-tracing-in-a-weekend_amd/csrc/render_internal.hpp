@@ -32,6 +32,7 @@ struct Sink {
     // of the shard's tiles once this range is in
     const rtk::AdaptiveFrame* moments = nullptr;
     int n_done = 0;
+    const rtk::AdaptiveHalves* halves = nullptr;   // rt_render_adaptive_halves: the half sums beside them
 };
 
 // What a plan launches: the scene's device view with the plan's staged counts, and the launch

@@ -172,11 +172,24 @@ struct AdaptiveFrame {
     const uint32_t* order;
     int32_t width, height, tiles_x, pos_begin;
 };
+// rt_render_adaptive_halves: the RGB sums of the samples with an even (a) and with an odd (b)
+// global sample index, summed as AdaptiveFrame::sum is and laid out like it. A struct of its own,
+// passed to the moments kernel after its other arguments: rt_render_adaptive's instantiation takes
+// the AdaptiveFrame it always took, at the same argument offsets.
+struct AdaptiveHalves {
+    double* sum_a;        // height x width x 3: closed chunks, even samples
+    double* sum_a_open;   // height x width x 3: the chunk in progress between buffer batches
+    double* sum_b;        // the same of the odd samples
+    double* sum_b_open;
+};
 // a batch of n_samples records per pixel of the shard's n_tiles tiles (tiled_record order) added to
 // the frame's moments; pos = samples of the open chunk seen before this batch; close: the pass's
-// last batch (ends the chunk, writes tile_error / tile_spp = n_done for the shard's tiles)
+// last batch (ends the chunk, writes tile_error / tile_spp = n_done for the shard's tiles).
+// halves (null: rt_render_adaptive's kernel) also takes the two half sums; first = the global index
+// of the batch's first sample, whose parity no chunk position gives when the chunk is odd.
 hipError_t launch_adaptive_moments(const double* samples, const AdaptiveFrame& F, int n_tiles, int n_samples,
-                                   int chunk, int pos, bool close, int n_done, hipStream_t stream);
+                                   int chunk, int pos, bool close, int n_done, hipStream_t stream,
+                                   const AdaptiveHalves* halves = nullptr, int first = 0);
 // order_out = [order_in's first n_stopped | the others that now stop | the others that go on];
 // a tile stops when at_max or (threshold > 0 and tile_error <= threshold); counts = {stopped, active}
 hipError_t launch_adaptive_compact(const uint32_t* order_in, uint32_t* order_out, const double* tile_error,
@@ -185,5 +198,10 @@ hipError_t launch_adaptive_compact(const uint32_t* order_in, uint32_t* order_out
 // mean (f32 / f64) = sum * (1 / tile_spp of the pixel's tile); se_map (may be null) = per-pixel se
 hipError_t launch_adaptive_resolve(const double* sum, const double* q, const uint32_t* tile_spp, void* mean, bool f64,
                                    double* se_map, int width, int height, hipStream_t stream);
+// mean_a = sum_a * (1 / n_a), mean_b = sum_b * (1 / n_b) (f32 / f64); n = tile_spp of the pixel's
+// tile (>= 2), n_a = (n + 1) / 2, n_b = n / 2
+hipError_t launch_adaptive_resolve_halves(const double* sum_a, const double* sum_b, const uint32_t* tile_spp,
+                                          void* mean_a, void* mean_b, bool f64, int width, int height,
+                                          hipStream_t stream);
 
 }  // namespace rtk

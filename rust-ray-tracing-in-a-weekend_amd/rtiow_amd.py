@@ -83,6 +83,7 @@ EXPORTED = [
     "rt_denoise", "rt_denoise_host", "rt_denoise_last_stats",
     "rt_render_features", "rt_features_last_stats", "rt_denoise_guided", "rt_denoise_guided_host",
     "rt_denoise_atrous", "rt_denoise_atrous_host", "rt_atrous_last_stats",
+    "rt_render_adaptive_halves", "rt_denoise_cross", "rt_denoise_cross_host", "rt_cross_last_stats",
 ]
 
 # int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_total)
@@ -180,6 +181,11 @@ class AdaptiveOut(ctypes.Structure):
                 ("stderr_map", ctypes.c_void_p)]
 
 
+class AdaptiveHalves(ctypes.Structure):
+    """rt_adaptive_halves: both required."""
+    _fields_ = [("mean_a", ctypes.c_void_p), ("mean_b", ctypes.c_void_p)]
+
+
 class AdaptiveStats(ctypes.Structure):
     """rt_adaptive_stats: the last rt_render_adaptive of a context."""
     _fields_ = [("passes", ctypes.c_int32), ("min_spp", ctypes.c_int32), ("step_spp", ctypes.c_int32),
@@ -254,6 +260,29 @@ class AtrousStats(ctypes.Structure):
 ATROUS_LEVELS = 3
 ATROUS_SIGMA_L = 2.0
 
+
+class CrossParams(ctypes.Structure):
+    """rt_cross_params."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("format", ctypes.c_int32),
+                ("on_device", ctypes.c_int32), ("radius", ctypes.c_int32), ("patch", ctypes.c_int32),
+                ("k", ctypes.c_double), ("variance_scale", ctypes.c_double), ("stream", ctypes.c_void_p)]
+
+
+class CrossStats(ctypes.Structure):
+    """rt_cross_stats: the last rt_denoise_cross of a context."""
+    _fields_ = [("kernel_ms", ctypes.c_double), ("radius", ctypes.c_int32), ("patch", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("scratch_bytes", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# rt_denoise_cross's default variance_scale: the two halves of an evenly split mean each have twice
+# its variance (rt_abi.h), and of {1, 2, 4} it gives the lowest RMSE on C2 at threshold 0.02 with
+# rt_denoise's default window (10, 3, 0.45), which the cross filter keeps (DESIGN.md 5.12,
+# profiles/cross_scale*_c2_10_3.log)
+CROSS_VARIANCE_SCALE = 2.0
+
 _lib = None
 
 
@@ -326,6 +355,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_cost_tile_order": ([P, ctypes.c_int64, P], I),
         "rt_render_adaptive": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
                                 ctypes.POINTER(AdaptiveParams), ctypes.POINTER(AdaptiveOut)], I),
+        "rt_render_adaptive_halves": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
+                                       ctypes.POINTER(AdaptiveParams), ctypes.POINTER(AdaptiveOut),
+                                       ctypes.POINTER(AdaptiveHalves)], I),
         "rt_adaptive_last_stats": ([P, ctypes.POINTER(AdaptiveStats)], I),
         "rt_adaptive_tile_errors_host": ([P, P, P, I, I, P, P], I),
         "rt_denoise": ([P, ctypes.POINTER(DenoiseParams), P, P, P], I),
@@ -339,6 +371,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_denoise_atrous": ([P, ctypes.POINTER(AtrousParams), P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
         "rt_denoise_atrous_host": ([ctypes.POINTER(AtrousParams), P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
         "rt_atrous_last_stats": ([P, ctypes.POINTER(AtrousStats)], I),
+        "rt_denoise_cross": ([P, ctypes.POINTER(CrossParams), P, P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
+        "rt_denoise_cross_host": ([ctypes.POINTER(CrossParams), P, P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
+        "rt_cross_last_stats": ([P, ctypes.POINTER(CrossStats)], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name, None)
@@ -740,6 +775,38 @@ def denoise_atrous_host(mean, se, albedo=None, normal=None, depth=None, sigmas=G
     return out, se_out
 
 
+def _cross_args(mean_a, mean_b, se, radius, patch, k, variance_scale):
+    """(params, mean_a, mean_b, se) of a host-pointer cross call: the half means as _denoise_args
+    takes a mean, both of one format and shape."""
+    d, a, s = _denoise_args(mean_a, se, radius, patch, k)
+    b = np.asarray(mean_b)
+    b = np.ascontiguousarray(b, dtype=np.float32 if b.dtype == np.float32 else np.float64)
+    if b.shape != a.shape or b.dtype != a.dtype:
+        raise RTError(f"denoise_cross: mean_b is {b.shape} {b.dtype}, mean_a {a.shape} {a.dtype}")
+    p = CrossParams(d.width, d.height, d.format, 0, int(radius), int(patch), float(k), float(variance_scale), None)
+    return p, a, b, s
+
+
+def denoise_cross_host(mean_a, mean_b, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
+                       radius: int = 10, patch: int = 3, k: float = 0.45,
+                       variance_scale: float = CROSS_VARIANCE_SCALE, want_stderr: bool = True):
+    """rt_denoise_cross_host: the cross-filtered NL-means over two half frames (rt_abi.h) on the host,
+    no device needed. mean_a, mean_b: height x width x 3, both f32 or both f64; se: the whole mean's
+    standard error, height x width; the guides as denoise_guided_host takes them. Returns (the
+    filtered frame in the means' format, the standard error the halves' disagreement leaves in it,
+    height x width f64, or None without want_stderr)."""
+    lib = load_library()
+    p, a, b, s = _cross_args(mean_a, mean_b, se, radius, patch, k, variance_scale)
+    g, keep = _guide_args(a.shape[:2], albedo, normal, depth, sigmas)
+    out = np.empty_like(a)
+    se_out = np.empty_like(s) if want_stderr else None
+    _check(lib.rt_denoise_cross_host(ctypes.byref(p), a.ctypes.data, b.ctypes.data, s.ctypes.data, ctypes.byref(g),
+                                     out.ctypes.data, se_out.ctypes.data if want_stderr else None),
+           "rt_denoise_cross_host")
+    del keep
+    return out, se_out
+
+
 def write_ppm(rgb: np.ndarray, path: str, samples_per_pixel: int = 1) -> None:
     """P3 writer of the reference (write_color, math.rs:119-132; main.rs:472, 591-596):
     height x width x 3, row 0 = bottom. An f64 array takes rt_write_ppm_f64 — the reference's
@@ -871,6 +938,40 @@ class Renderer:
         _check(self.lib.rt_render_adaptive(self.h, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(ap),
                                            ctypes.byref(out)), "rt_render_adaptive")
 
+    def render_adaptive_halves(self, camera: Camera, params: RenderParams, min_spp: int, step_spp: int,
+                               threshold: float):
+        """rt_render_adaptive_halves: render_adaptive's (mean, tile_spp, tile_error, stderr_map), bit
+        for bit, and after them the means of every pixel's even and of its odd samples (mean_a,
+        mean_b: height x width x 3 of the frame's format), rt_denoise_cross's input."""
+        W, H = params.width, params.height
+        ty, tx = (H + 7) // 8, (W + 7) // 8
+        dt = np.float64 if params.out_format == RT_OUT_F64 else np.float32
+        mean, mean_a, mean_b = (np.empty((H, W, 3), dtype=dt) for _ in range(3))
+        tile_spp = np.zeros((ty, tx), dtype=np.uint32)
+        tile_error = np.zeros((ty, tx), dtype=np.float64)
+        se = np.empty((H, W), dtype=np.float64)
+        params.out_on_device = 0
+        ap = AdaptiveParams(int(min_spp), int(step_spp), float(threshold))
+        out = AdaptiveOut(mean.ctypes.data, tile_spp.ctypes.data, tile_error.ctypes.data, se.ctypes.data)
+        hv = AdaptiveHalves(mean_a.ctypes.data, mean_b.ctypes.data)
+        _check(self.lib.rt_render_adaptive_halves(self.h, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(ap),
+                                                  ctypes.byref(out), ctypes.byref(hv)), "rt_render_adaptive_halves")
+        return mean, tile_spp, tile_error, se, mean_a, mean_b
+
+    def render_adaptive_halves_device(self, camera: Camera, params: RenderParams, min_spp: int, step_spp: int,
+                                      threshold: float, mean_ptr: int, mean_a_ptr: int, mean_b_ptr: int,
+                                      stderr_ptr: int = 0, tile_spp_ptr: int = 0, tile_error_ptr: int = 0,
+                                      stream: Optional[int] = None):
+        """rt_render_adaptive_halves into device buffers: as render_adaptive_device, with the two half
+        means (height x width x 3 of params.out_format each). The call itself is synchronous."""
+        params.out_on_device = 1
+        params.stream = stream
+        ap = AdaptiveParams(int(min_spp), int(step_spp), float(threshold))
+        out = AdaptiveOut(mean_ptr, tile_spp_ptr or None, tile_error_ptr or None, stderr_ptr or None)
+        hv = AdaptiveHalves(mean_a_ptr or None, mean_b_ptr or None)
+        _check(self.lib.rt_render_adaptive_halves(self.h, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(ap),
+                                                  ctypes.byref(out), ctypes.byref(hv)), "rt_render_adaptive_halves")
+
     def denoise(self, mean, se, radius: int = 10, patch: int = 3, k: float = 0.45) -> np.ndarray:
         """rt_denoise on host arrays (synchronous): mean height x width x 3 f32 or f64, se height x
         width, as render_adaptive returns them. Returns the filtered frame in mean's format."""
@@ -948,6 +1049,43 @@ class Renderer:
     def atrous_stats(self) -> AtrousStats:
         s = AtrousStats()
         _check(self.lib.rt_atrous_last_stats(self.h, ctypes.byref(s)), "rt_atrous_last_stats")
+        return s
+
+    def denoise_cross(self, mean_a, mean_b, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
+                      radius: int = 10, patch: int = 3, k: float = 0.45,
+                      variance_scale: float = CROSS_VARIANCE_SCALE, want_stderr: bool = True):
+        """rt_denoise_cross on host arrays (synchronous): NL-means over two half frames, each filtered
+        with the other's weights; arguments and result as the module's denoise_cross_host."""
+        p, a, b, s = _cross_args(mean_a, mean_b, se, radius, patch, k, variance_scale)
+        g, keep = _guide_args(a.shape[:2], albedo, normal, depth, sigmas)
+        out = np.empty_like(a)
+        se_out = np.empty_like(s) if want_stderr else None
+        _check(self.lib.rt_denoise_cross(self.h, ctypes.byref(p), a.ctypes.data, b.ctypes.data, s.ctypes.data,
+                                         ctypes.byref(g), out.ctypes.data, se_out.ctypes.data if want_stderr else None),
+               "rt_denoise_cross")
+        del keep
+        return out, se_out
+
+    def denoise_cross_device(self, mean_a_ptr: int, mean_b_ptr: int, stderr_ptr: int, out_ptr: int, width: int,
+                             height: int, albedo_ptr: int = 0, normal_ptr: int = 0, depth_ptr: int = 0,
+                             sigmas=GUIDE_SIGMAS, out_format: int = RT_OUT_F32, radius: int = 10, patch: int = 3,
+                             k: float = 0.45, variance_scale: float = CROSS_VARIANCE_SCALE, stderr_out_ptr: int = 0,
+                             stream: Optional[int] = None):
+        """Enqueues rt_denoise_cross over device buffers on `stream`: as denoise_guided_device, with
+        the two half means; stderr_out_ptr (height x width f64; 0 leaves it out) receives the error
+        map."""
+        p = CrossParams(int(width), int(height), int(out_format), 1, int(radius), int(patch), float(k),
+                        float(variance_scale), stream)
+        sa, sn, sz = (float(v) for v in sigmas)
+        g = DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+        _check(self.lib.rt_denoise_cross(self.h, ctypes.byref(p), ctypes.c_void_p(mean_a_ptr),
+                                         ctypes.c_void_p(mean_b_ptr), ctypes.c_void_p(stderr_ptr), ctypes.byref(g),
+                                         ctypes.c_void_p(out_ptr), ctypes.c_void_p(stderr_out_ptr or None)),
+               "rt_denoise_cross")
+
+    def cross_stats(self) -> CrossStats:
+        s = CrossStats()
+        _check(self.lib.rt_cross_last_stats(self.h, ctypes.byref(s)), "rt_cross_last_stats")
         return s
 
     def render_features(self, camera: Camera, params: RenderParams, albedo: bool = True, normal: bool = True,

@@ -29,10 +29,16 @@ with the guided kernel's time. --parent-denoise: the parent library filters its 
 (at --features SPP, default 16; the --guided sigmas, else the binding's) as edge stops; rmse_atrous,
 the summed level kernels' time and the mean of the filter's stderr_out are reported beside the
 others. --demodulate (with --atrous): it filters colour / albedo.
+--cross R F K [SCALE]: the adaptive modes render through rt_render_adaptive_halves (the same frame and
+error map) and the two half means go through rt_denoise_cross (variance_scale SCALE, default 2; the
+--guided sigmas with the feature buffers if given); rmse_cross and the cross kernels' time are reported
+beside the others, and the honesty of its error map: rms(stderr_out) over the RMSE of Y(out), linear,
+against the same reference (atrous_honesty: rt_denoise_atrous's stderr_out by the same yardstick).
 
 usage: python scripts/adaptive_bench.py --config C2 --thresholds 0.02 0.01 0.005 \
            [--parent lib/librtiow_parent.so] [--min-spp 64 --step-spp 64] [--denoise 10 3 0.45]
            [--features 16] [--guided 0.1 0.2 0.1] [--parent-denoise] [--atrous 5 4.0 [--demodulate]]
+           [--cross 10 3 0.45 2.0]
            [--out adaptive_c2.json]
 """
 import argparse
@@ -62,17 +68,23 @@ cam, bg = rt.scene_camera(a["scene"], W, H)
 r = rt.Renderer(0)
 r.upload(world)
 gamma = lambda x: np.sqrt(np.clip(x.astype(np.float64), 0.0, 0.999))
-ref = None
+ref = ref_y = None
+luma = lambda x: (lambda c: 0.2126 * c[..., 0] + 0.7152 * c[..., 1] + 0.0722 * c[..., 2])(x.astype(np.float64))
+def honesty(out, se_out):   # rms(stderr_out) / RMSE of Y(out), linear
+    return float(np.sqrt(np.mean(se_out ** 2)) / np.sqrt(np.mean((luma(out) - ref_y) ** 2)))
 if a["ref"]:
     if not os.path.exists(a["ref"]):
         p = rt.Renderer.params(W, H, spp * a["ref_mult"], a["depth"], bg, 2, out_format=rt.RT_OUT_F32)
         np.save(a["ref"], r.render(cam, p))
+    ref_y = luma(np.load(a["ref"]))
     ref = gamma(np.load(a["ref"]))
 res = {{}}
 dn = a.get("denoise")
 ft, gd = a.get("features"), a.get("guided")
 at = a.get("atrous")
+cx = a.get("cross")
 uniform_se = []
+uniform_halves = []
 guides = []
 def features(d):
     pf = rt.Renderer.params(W, H, ft, a["depth"], bg, 1, out_format=rt.RT_OUT_F64)
@@ -98,6 +110,29 @@ def atrous(mode, img, se, d):
     d["atrous_wall_ms"] = (time.perf_counter() - t0) * 1e3
     st = r.atrous_stats()
     d.update(atrous_kernel_ms=st.kernel_ms, atrous_scratch_bytes=st.scratch_bytes, atrous_mean_stderr_out=float(se_out.mean()))
+    if ref_y is not None:
+        d["atrous_honesty"] = honesty(out, se_out)
+    return out
+def cross(mode, halves, se, d):
+    se = error_map(mode, se)
+    if mode == "uniform":
+        if not uniform_halves:   # the same frame's halves: an adaptive call that never stops early
+            p = rt.Renderer.params(W, H, spp, a["depth"], bg, 1, out_format=rt.RT_OUT_F32)
+            uniform_halves.append(r.render_adaptive_halves(cam, p, a["min_spp"], a["step_spp"], 0.0)[4:])
+        halves = uniform_halves[0]
+    g = guides[0] if gd else (None, None, None)
+    t0 = time.perf_counter()
+    out, se_out = r.denoise_cross(halves[0], halves[1], se, *g, gd or rt.GUIDE_SIGMAS, int(cx[0]), int(cx[1]), float(cx[2]),
+                                  float(cx[3]))
+    d["cross_wall_ms"] = (time.perf_counter() - t0) * 1e3
+    st = r.cross_stats()
+    d.update(cross_kernel_ms=st.kernel_ms, cross_lds_bytes=st.lds_bytes, cross_scratch_bytes=st.scratch_bytes,
+             cross_rms_stderr_out=float(np.sqrt(np.mean(se_out ** 2))))
+    if ref_y is not None:
+        d["cross_honesty"] = honesty(out, se_out)
+    r.denoise_cross(halves[0], halves[1], se, *g, gd or rt.GUIDE_SIGMAS, int(cx[0]), int(cx[1]), float(cx[2]), float(cx[3]),
+                    want_stderr=False)
+    d["cross_kernel_ms_no_stderr"] = r.cross_stats().kernel_ms
     return out
 def denoised(mode, img, se, d):
     se = error_map(mode, se)
@@ -120,31 +155,39 @@ def run(mode):
         img = r.render(cam, p)
         ms = (time.perf_counter() - t0) * 1e3
         st = r.stats()
-        return img, None, dict(wall_ms=ms, trace_ms=st.kernel_ms, reduce_ms=st.reduce_ms, samples=st.samples,
-                               schedule=st.schedule, n_batches=st.n_batches)
-    img, tile_spp, tile_err, se = r.render_adaptive(cam, p, a["min_spp"], a["step_spp"], float(mode))
+        return img, None, None, dict(wall_ms=ms, trace_ms=st.kernel_ms, reduce_ms=st.reduce_ms, samples=st.samples,
+                                     schedule=st.schedule, n_batches=st.n_batches)
+    halves = None
+    if cx:
+        img, tile_spp, tile_err, se, *halves = r.render_adaptive_halves(cam, p, a["min_spp"], a["step_spp"], float(mode))
+    else:
+        img, tile_spp, tile_err, se = r.render_adaptive(cam, p, a["min_spp"], a["step_spp"], float(mode))
     ms = (time.perf_counter() - t0) * 1e3
     st = r.adaptive_stats()
     d = st.as_dict()
     d.update(wall_ms=ms, reduce_ms=st.moments_ms, samples=st.samples_traced, mean_tile_spp=float(tile_spp.mean()),
              tiles_at_max=int((tile_spp == spp).sum()), tiles_at_min=int((tile_spp == st.min_spp).sum()),
              tile_error_pct=[float(x) for x in np.percentile(tile_err, [5, 25, 50, 75, 95, 100])])
-    return img, se, d
+    d["halves"] = int(bool(cx))
+    return img, se, halves, d
 for mode in a["modes"]:
-    img, se, d = run(mode)                     # warm-up: code objects, buffers
+    img, se, halves, d = run(mode)             # warm-up: code objects, buffers
     if ft:
         features(d)
     if dn:
         denoised(mode, img, se, d)
     if at:
         atrous(mode, img, se, d)
+    if cx:
+        cross(mode, halves, se, d)
 for _ in range(a["reps"]):
     for mode in a["modes"]:
-        img, se, d = run(mode)
+        img, se, halves, d = run(mode)
         if ft:
             features(d)
         out, out_g = denoised(mode, img, se, d) if dn else (None, None)
         out_a = atrous(mode, img, se, d) if at else None
+        out_x = cross(mode, halves, se, d) if cx else None
         e = res.setdefault(mode, dict(runs=[]))
         e["runs"].append(d)
         if ref is not None and "rmse" not in e:
@@ -155,6 +198,8 @@ for _ in range(a["reps"]):
                 e["rmse_guided"] = float(np.sqrt(np.mean((gamma(out_g) - ref) ** 2)))
             if out_a is not None:
                 e["rmse_atrous"] = float(np.sqrt(np.mean((gamma(out_a) - ref) ** 2)))
+            if out_x is not None:
+                e["rmse_cross"] = float(np.sqrt(np.mean((gamma(out_x) - ref) ** 2)))
 print("RESULT", json.dumps(res))
 print("BUILD", rt.build_info())
 """
@@ -186,13 +231,19 @@ def main():
     ap.add_argument("--atrous", type=float, nargs=2, default=None, metavar=("LEVELS", "SIGMA_L"),
                     help="also filter every frame with rt_denoise_atrous (guided by the feature buffers)")
     ap.add_argument("--demodulate", action="store_true", help="with --atrous: filter colour / albedo")
+    ap.add_argument("--cross", type=float, nargs="+", default=None, metavar="R F K [SCALE]",
+                    help="also filter the two half frames of every mode with rt_denoise_cross")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.cross:
+        if len(a.cross) not in (3, 4):
+            ap.error("--cross takes R F K [SCALE]")
+        a.cross = list(a.cross) + [2.0] * (4 - len(a.cross))
     if a.guided and not a.denoise:
         ap.error("--guided needs --denoise R F K")
     if a.demodulate and not a.atrous:
         ap.error("--demodulate needs --atrous LEVELS SIGMA_L")
-    if (a.guided or a.atrous) and not a.features:
+    if (a.guided or a.atrous) and not a.features:   # (--cross alone runs unguided)
         a.features = 16
     cfg = CONFIGS[a.config]
     tmp = tempfile.TemporaryDirectory()   # the error reference: rendered by the first child, read by the others
@@ -208,7 +259,7 @@ def main():
             if a.denoise and (name == "new" or a.parent_denoise):
                 args["denoise"] = a.denoise
             if name == "new":
-                args.update(features=a.features, guided=a.guided, atrous=a.atrous, demodulate=a.demodulate)
+                args.update(features=a.features, guided=a.guided, atrous=a.atrous, demodulate=a.demodulate, cross=a.cross)
             env = dict(os.environ, RT_LIB_PATH=os.path.abspath(os.path.join(REPO, lib)))
             out = subprocess.run([sys.executable, "-c", CHILD.format(repo=REPO, args=json.dumps(args))], env=env,
                                  capture_output=True, text=True, timeout=900)
@@ -221,7 +272,8 @@ def main():
                 print(f"  {name}: rt_build_info {builds[name]}", flush=True)
             for mode, e in d.items():
                 k = runs.setdefault(f"{name}:{mode}", dict(runs=[], rmse=e.get("rmse"), rmse_denoised=e.get("rmse_denoised"),
-                                                           rmse_guided=e.get("rmse_guided"), rmse_atrous=e.get("rmse_atrous")))
+                                                           rmse_guided=e.get("rmse_guided"), rmse_atrous=e.get("rmse_atrous"),
+                                                           rmse_cross=e.get("rmse_cross")))
                 k["runs"] += e["runs"]
                 print(f"  {name}:{mode}: wall {['%.2f' % x['wall_ms'] for x in e['runs']]}", flush=True)
     uniform_px = cfg["width"] * cfg["height"] * cfg["spp"]
@@ -258,6 +310,16 @@ def main():
                      atrous_wall_ms=median([x["atrous_wall_ms"] for x in rs]), atrous=a.atrous, demodulate=int(a.demodulate),
                      atrous_scratch_bytes=rs[0]["atrous_scratch_bytes"],
                      atrous_mean_stderr_out=median([x["atrous_mean_stderr_out"] for x in rs]))
+        if "atrous_honesty" in rs[0]:
+            s["atrous_honesty"] = rs[0]["atrous_honesty"]
+        if "cross_kernel_ms" in rs[0]:
+            s.update(rmse_cross=e["rmse_cross"], cross=a.cross, cross_kernel_ms=median([x["cross_kernel_ms"] for x in rs]),
+                     cross_kernel_ms_min=min(x["cross_kernel_ms"] for x in rs),
+                     cross_kernel_ms_max=max(x["cross_kernel_ms"] for x in rs),
+                     cross_kernel_ms_no_stderr=median([x["cross_kernel_ms_no_stderr"] for x in rs]),
+                     cross_wall_ms=median([x["cross_wall_ms"] for x in rs]), cross_lds_bytes=rs[0]["cross_lds_bytes"],
+                     cross_scratch_bytes=rs[0]["cross_scratch_bytes"], cross_rms_stderr_out=rs[0]["cross_rms_stderr_out"],
+                     cross_honesty=rs[0].get("cross_honesty"), halves=rs[0].get("halves"))
         for k in ("passes", "classify_ms", "mean_tile_spp", "tiles_at_max", "tiles_at_min", "tiles", "schedule", "n_batches",
                   "max_pass_batches"):
             if k in rs[0]:
@@ -274,6 +336,8 @@ def main():
             doc["guided"] = a.guided
         if a.atrous:
             doc.update(atrous=a.atrous, demodulate=int(a.demodulate))
+        if a.cross:
+            doc["cross"] = a.cross
         json.dump(doc, open(a.out, "w"), indent=1)
 
 
