@@ -39,6 +39,8 @@
  *                             of the odd samples
  *   rt_denoise_cross          (new) rt_denoise over two half frames, each filtered with the other's
  *                             weights, with the error left read off their difference
+ *   rt_denoise_pyramid        (new) rt_denoise_guided run at several scales of the frame, the coarse
+ *                             scales supplying the low frequencies its window cannot see
  *
  * Threading: a context is bound to one device and is used by one host thread at
  * a time. Worlds are plain host objects.
@@ -803,6 +805,79 @@ typedef struct rt_cross_stats {
     int64_t scratch_bytes;   /* e scratch that call used: 0 without stderr_out, else 8 width height */
 } rt_cross_stats;
 int rt_cross_last_stats(rt_ctx* ctx, rt_cross_stats* out);
+
+/* ---- multi-scale NL-means (additive to ABI v6: new symbols only) --------------------------------
+ * The NL-means filters see at most a 21 x 21 window, so noise broader than the window survives as
+ * low-frequency blotches. The pyramid answer (as in ray-histogram fusion, Delbracio et al. 2014):
+ * the frame is reduced by 2 x 2 block means L - 1 times, rt_denoise_guided filters every level with
+ * the same (radius, patch, k), and from the coarsest level down each level's result is corrected by
+ * what the filtered coarser level knows better: its low frequencies. A window of radius r over L
+ * levels covers a footprint of radius r 2^(L-1); the pixels of all levels sum to less than 4/3 of
+ * the frame's.
+ *
+ * Inputs: M, se, the optional guides g, radius, patch and k exactly as rt_denoise_guided takes them;
+ * levels L in 1..5. All arithmetic is f64 with no contraction and no fast math; f32 input is widened
+ * first. "In raster order" means dy outer, dx inner, starting from 0.0.
+ * Level frames. Level 0 is w_0 x h_0 = width x height; level l + 1 is w_{l+1} = (w_l + 1) / 2 by
+ *   h_{l+1} = (h_l + 1) / 2 (integer division). A level may be 1 x 1.
+ * Blocks. The block of a coarse pixel c = (cx, cy) is the set of level-l pixels (2 cx + i, 2 cy + j),
+ *   i, j in {0, 1}, that lie inside the level-l frame; n is their number (1, 2 or 4) as a double.
+ * Down. C_0 = M, s_0 = se. Per channel, C_{l+1}(c) = the raster-order sum of C_l over the block,
+ *   divided by n. s_{l+1}(c) = sqrt(T) / n, T the raster-order sum of s_l(a) s_l(a) over the block:
+ *   the standard error of a mean of independent pixels. Each guide frame given (A, N, Z) is reduced
+ *   exactly as C is; the sigmas are every level's. Non-finite values get no special rule here: they
+ *   go through the sums.
+ * Per level. D_l = rt_denoise_guided's filter, exactly as its contract states it, on (C_l, s_l, the
+ *   level's guides, radius, patch, k) at the level's size, kept in f64.
+ * Up, for l = L - 2 down to 0, with R_{L-1} = D_{L-1}:
+ *   B_l(c) = the block mean of D_l, by the Down rule
+ *   K_l(c) = R_{l+1}(c) - B_l(c), per channel
+ *   for a level-l pixel p = (x, y): cx = x / 2; ox = cx - 1 if x is even, else cx + 1, clamped to
+ *   [0, w_{l+1} - 1]; cy and oy likewise from y and h_{l+1}. The taps, in this order: (cx, cy) with
+ *   weight 9/16, (ox, cy) with 3/16, (cx, oy) with 3/16, (ox, oy) with 1/16; a clamped tap may repeat
+ *   a pixel and is still taken. A tap is taken if all three channels of K_l there are finite.
+ *   u(p) = (sum weight K_l) / (sum weight) over the taps taken, both sums in tap order from 0.0;
+ *   u(p) = 0 if no tap is taken
+ *   R_l(p) = D_l(p) + u(p)
+ * Output: out = R_0 in M's format; an f32 out is the f64 value rounded once. Where Y(M(p)) or se(p)
+ * is not finite, out(p) is M(p) bit for bit: a non-finite pixel stays where it is. A non-finite
+ * colour makes K of the blocks that contain it non-finite at every level, which removes those
+ * correction taps and nothing else; a pixel whose se alone is not finite is kept at every level
+ * (s of its blocks is not finite either) and its blocks' K stays finite.
+ * Consequences: L = 1 is rt_denoise_guided (without guides rt_denoise) bit for bit. Nothing depends
+ * on the device's tiling: the result repeats bit for bit, and the device and host filters differ
+ * only by their exp. */
+typedef struct rt_pyramid_params {
+    int32_t width, height, format, on_device;  /* as rt_denoise_params */
+    int32_t radius, patch;                     /* as rt_denoise: 1..10, 0..3 */
+    double k;                                  /* > 0 and finite */
+    int32_t levels;                            /* L in 1..5 */
+    int32_t reserved0;                         /* must be 0 */
+    void* stream;        /* hipStream_t (NULL = the context's stream) */
+} rt_pyramid_params;
+/* RT_ERR_INVALID as rt_denoise_guided returns it, and for levels outside 1..5 or reserved0 != 0.
+ * Needs no uploaded scene. Every pointer is a device pointer iff p->on_device; with it set the call
+ * is only enqueued, like rt_denoise. At L = 1 the call is rt_denoise_guided's one launch on the
+ * caller's buffers and uses no scratch. At L >= 2 the levels' f64 frames (C_l, s_l, the guides given
+ * and D_l of every level above 0, D_0, the widened frame when M is f32, and one K frame of level
+ * 1's size) live in scratch the context owns, allocated on first need and grown when a call needs
+ * more: a call that grows it may wait for the stream, any other call with on_device set does no
+ * host-side wait. The filters of the levels above 0 are too few workgroups to fill a device, so
+ * they run on a stream of the context's own beside level 0's, ordered after Down and before Up by
+ * events: all of the call's work is complete when what it enqueued on its stream is. */
+int rt_denoise_pyramid(rt_ctx* ctx, const rt_pyramid_params* p, const void* mean, const double* stderr_map,
+                       const rt_denoise_guides* g /* may be NULL */, void* out);
+/* The same filter on the host, no device needed (on_device and stream are ignored). */
+int rt_denoise_pyramid_host(const rt_pyramid_params* p, const void* mean, const double* stderr_map,
+                            const rt_denoise_guides* g /* may be NULL */, void* out);
+
+typedef struct rt_pyramid_stats {
+    double kernel_ms;        /* last rt_denoise_pyramid: all its kernels (HIP events; waits if only enqueued) */
+    int32_t levels, radius, patch;
+    int32_t reserved0;
+    int64_t scratch_bytes;   /* level scratch that call used: 0 exactly when levels == 1 */
+} rt_pyramid_stats;
+int rt_pyramid_last_stats(rt_ctx* ctx, rt_pyramid_stats* out);
 
 /* ---- output ------------------------------------------------------------------------------ */
 /* P3 PPM byte for byte as the reference writes it (write_color, math.rs:119-132; main.rs:472,

@@ -105,6 +105,8 @@ int rt_ctx_create(int device, rt_ctx** out)
     if (e == hipSuccess) e = c->ev_ft.create();
     if (e == hipSuccess) e = c->ev_at.create();
     if (e == hipSuccess) e = c->ev_x.create();
+    if (e == hipSuccess) e = c->ev_py.create();
+    if (e == hipSuccess) e = c->ev_pf.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_done.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_in.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_tr.create(hipEventDisableTiming);

@@ -1,8 +1,9 @@
 // abi_filters.cpp — the post-filters behind the C ABI (include/rt/rt_abi.h): the variance-guided
 // NL-means filter (rt_denoise, rt_denoise_guided; denoise_kernel.hip), the variance-guided
-// a-trous wavelet filter (rt_denoise_atrous; atrous_kernel.hip) and the cross-filtered NL-means over
-// two half frames (rt_denoise_cross; cross_kernel.hip), with their stats. Their host counterparts
-// are denoise_host.cpp, atrous_host.cpp and cross_host.cpp.
+// a-trous wavelet filter (rt_denoise_atrous; atrous_kernel.hip), the cross-filtered NL-means over
+// two half frames (rt_denoise_cross; cross_kernel.hip) and the multi-scale NL-means
+// (rt_denoise_pyramid; pyramid_kernel.hip), with their stats. Their host counterparts are
+// denoise_host.cpp, atrous_host.cpp, cross_host.cpp and pyramid_host.cpp.
 #include <hip/hip_runtime.h>
 
 #include <initializer_list>
@@ -13,6 +14,7 @@
 #include "ctx_internal.hpp"
 #include "denoise.hpp"
 #include "filter_guides.hpp"
+#include "pyramid.hpp"
 
 namespace {
 
@@ -274,6 +276,68 @@ int rt_cross_last_stats(rt_ctx* c, rt_cross_stats* out)
         c->xstats.kernel_ms = ms[0];
     }
     *out = c->xstats;
+    return RT_OK;
+}
+
+// ---- multi-scale NL-means (rt_abi.h: the filter; pyramid_kernel.hip; pyramid_host.cpp) ------------
+int rt_denoise_pyramid(rt_ctx* c, const rt_pyramid_params* p, const void* mean, const double* stderr_map,
+                       const rt_denoise_guides* g, void* out)
+{
+    if (!c) return fail(RT_ERR_INVALID, "null argument");
+    rtk::DenoiseGuides G;
+    if (const char* bad = rtk::pyramid_check(p, mean, stderr_map, g, out, G)) return fail(RT_ERR_INVALID, bad);
+    const bool f64 = p->format == RT_OUT_F64, on_dev = p->on_device != 0;
+    const size_t hw = (size_t)p->width * (size_t)p->height;
+    const size_t frame_bytes = hw * 3 * (f64 ? 8 : 4);
+    const rtk::PyramidLayout lay(p->width, p->height, p->levels, f64, G.albedo != nullptr, G.normal != nullptr,
+                                 G.depth != nullptr);
+    const size_t scratch_bytes = lay.doubles * sizeof(double);
+
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = p->stream ? (hipStream_t)p->stream : c->stream;
+    StreamScope scope(c, stream);
+    int rc = scope.begin();
+    if (rc) return rc;
+    // the context's level scratch, grown on demand (a call of one level needs none and gets a null pointer)
+    rc = c->pyramid_buf.reserve(stream, scratch_bytes);
+    if (rc) return rc;
+    double* const scratch = scratch_bytes ? c->pyramid_buf.as<double>() : nullptr;
+
+    HostStage st;
+    FilterFrames f{mean, stderr_map, out, nullptr};
+    if (!on_dev) {
+        rc = stage_frames(st, stream, hw, frame_bytes, f, G);
+        if (rc) return rc;
+    }
+    HIP_TRY(c->ev_py.record(0, stream));
+    HIP_TRY(rtk::launch_pyramid(f.mean, f.se, f.out, f64, p->width, p->height, p->radius, p->patch, p->k, p->levels, G,
+                                scratch, stream, rtk::PyramidSide{c->tstream[0], c->ev_pf.ev[0], c->ev_pf.ev[1]}));
+    HIP_TRY(c->ev_py.record(1, stream));
+    c->pstats = rt_pyramid_stats{};
+    c->pstats.levels = p->levels;
+    c->pstats.radius = p->radius;
+    c->pstats.patch = p->patch;
+    c->pstats.scratch_bytes = (int64_t)scratch_bytes;
+    c->ev_py.arm();
+    rc = st.copy_back(stream);
+    if (rc) return rc;
+    rc = scope.end();
+    if (rc) return rc;
+    if (!on_dev) HIP_TRY(hipStreamSynchronize(stream));   // (the block is freed once its copies are done)
+    return RT_OK;
+}
+
+int rt_pyramid_last_stats(rt_ctx* c, rt_pyramid_stats* out)
+{
+    if (!c || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (c->ev_py.pending) {
+        HIP_TRY(hipSetDevice(c->device));
+        float ms[1] = {0};
+        const int rc = c->ev_py.resolve(ms);
+        if (rc) return rc;
+        c->pstats.kernel_ms = ms[0];
+    }
+    *out = c->pstats;
     return RT_OK;
 }
 

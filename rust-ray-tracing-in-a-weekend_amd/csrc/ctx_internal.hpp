@@ -167,6 +167,10 @@ struct rt_ctx {
     rt_cross_stats xstats{};            // the last rt_denoise_cross (rt_cross_last_stats)
     EventSpan<2> ev_x;                  //   around its kernels
     DevBuf cross_buf;                   //   e(p) between its two kernels (f64 per pixel; only with stderr_out)
+    rt_pyramid_stats pstats{};          // the last rt_denoise_pyramid (rt_pyramid_last_stats)
+    EventSpan<2> ev_py;                 //   around its kernels
+    DevBuf pyramid_buf;                 //   its levels' f64 frames (rtk::PyramidLayout; none at one level)
+    EventSpan<2> ev_pf;                 //   fork and join of its coarse levels' filters on tstream[0] (ordering events)
     // what a render's launch plan is made from (launch_plan.hpp): the uploaded scene, the device, the switches
     rtp::SceneFacts scene;
     rtp::DeviceFacts dev;

@@ -83,6 +83,7 @@ EXPORTED = [
     "rt_denoise", "rt_denoise_host", "rt_denoise_last_stats",
     "rt_render_features", "rt_features_last_stats", "rt_denoise_guided", "rt_denoise_guided_host",
     "rt_denoise_atrous", "rt_denoise_atrous_host", "rt_atrous_last_stats",
+    "rt_denoise_pyramid", "rt_denoise_pyramid_host", "rt_pyramid_last_stats",
     "rt_render_adaptive_halves", "rt_denoise_cross", "rt_denoise_cross_host", "rt_cross_last_stats",
 ]
 
@@ -277,6 +278,28 @@ class CrossStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PyramidParams(ctypes.Structure):
+    """rt_pyramid_params."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("format", ctypes.c_int32),
+                ("on_device", ctypes.c_int32), ("radius", ctypes.c_int32), ("patch", ctypes.c_int32),
+                ("k", ctypes.c_double), ("levels", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("stream", ctypes.c_void_p)]
+
+
+class PyramidStats(ctypes.Structure):
+    """rt_pyramid_stats: the last rt_denoise_pyramid of a context."""
+    _fields_ = [("kernel_ms", ctypes.c_double), ("levels", ctypes.c_int32), ("radius", ctypes.c_int32),
+                ("patch", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("scratch_bytes", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# rt_denoise_pyramid's defaults: the small window over three levels (DESIGN.md 5.13)
+PYRAMID_LEVELS = 3
+PYRAMID_WINDOW = (5, 2, 1.0)   # (radius, patch, k)
+
+
 # rt_denoise_cross's default variance_scale: the two halves of an evenly split mean each have twice
 # its variance (rt_abi.h), and of {1, 2, 4} it gives the lowest RMSE on C2 at threshold 0.02 with
 # rt_denoise's default window (10, 3, 0.45), which the cross filter keeps (DESIGN.md 5.12,
@@ -371,6 +394,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_denoise_atrous": ([P, ctypes.POINTER(AtrousParams), P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
         "rt_denoise_atrous_host": ([ctypes.POINTER(AtrousParams), P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
         "rt_atrous_last_stats": ([P, ctypes.POINTER(AtrousStats)], I),
+        "rt_denoise_pyramid": ([P, ctypes.POINTER(PyramidParams), P, P, ctypes.POINTER(DenoiseGuides), P], I),
+        "rt_denoise_pyramid_host": ([ctypes.POINTER(PyramidParams), P, P, ctypes.POINTER(DenoiseGuides), P], I),
+        "rt_pyramid_last_stats": ([P, ctypes.POINTER(PyramidStats)], I),
         "rt_denoise_cross": ([P, ctypes.POINTER(CrossParams), P, P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
         "rt_denoise_cross_host": ([ctypes.POINTER(CrossParams), P, P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
         "rt_cross_last_stats": ([P, ctypes.POINTER(CrossStats)], I),
@@ -775,6 +801,28 @@ def denoise_atrous_host(mean, se, albedo=None, normal=None, depth=None, sigmas=G
     return out, se_out
 
 
+def _pyramid_args(mean, se, radius, patch, k, levels):
+    """(params, mean, se) of a host-pointer pyramid call: mean and se as _denoise_args takes them."""
+    d, m, s = _denoise_args(mean, se, radius, patch, k)
+    return PyramidParams(d.width, d.height, d.format, 0, d.radius, d.patch, d.k, int(levels), 0, None), m, s
+
+
+def denoise_pyramid_host(mean, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
+                         radius: int = PYRAMID_WINDOW[0], patch: int = PYRAMID_WINDOW[1], k: float = PYRAMID_WINDOW[2],
+                         levels: int = PYRAMID_LEVELS) -> np.ndarray:
+    """rt_denoise_pyramid_host: the multi-scale NL-means filter (rt_abi.h) on the host, no device
+    needed. mean, se and the guides as denoise_guided_host takes them. Returns the filtered frame in
+    mean's format."""
+    lib = load_library()
+    p, m, s = _pyramid_args(mean, se, radius, patch, k, levels)
+    g, keep = _guide_args(m.shape[:2], albedo, normal, depth, sigmas)
+    out = np.empty_like(m)
+    _check(lib.rt_denoise_pyramid_host(ctypes.byref(p), m.ctypes.data, s.ctypes.data, ctypes.byref(g), out.ctypes.data),
+           "rt_denoise_pyramid_host")
+    del keep
+    return out
+
+
 def _cross_args(mean_a, mean_b, se, radius, patch, k, variance_scale):
     """(params, mean_a, mean_b, se) of a host-pointer cross call: the half means as _denoise_args
     takes a mean, both of one format and shape."""
@@ -1049,6 +1097,38 @@ class Renderer:
     def atrous_stats(self) -> AtrousStats:
         s = AtrousStats()
         _check(self.lib.rt_atrous_last_stats(self.h, ctypes.byref(s)), "rt_atrous_last_stats")
+        return s
+
+    def denoise_pyramid(self, mean, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
+                        radius: int = PYRAMID_WINDOW[0], patch: int = PYRAMID_WINDOW[1], k: float = PYRAMID_WINDOW[2],
+                        levels: int = PYRAMID_LEVELS) -> np.ndarray:
+        """rt_denoise_pyramid on host arrays (synchronous): denoise_guided run at `levels` scales of the
+        frame; arguments and result as the module's denoise_pyramid_host."""
+        p, m, s = _pyramid_args(mean, se, radius, patch, k, levels)
+        g, keep = _guide_args(m.shape[:2], albedo, normal, depth, sigmas)
+        out = np.empty_like(m)
+        _check(self.lib.rt_denoise_pyramid(self.h, ctypes.byref(p), m.ctypes.data, s.ctypes.data, ctypes.byref(g),
+                                           out.ctypes.data), "rt_denoise_pyramid")
+        del keep
+        return out
+
+    def denoise_pyramid_device(self, mean_ptr: int, stderr_ptr: int, out_ptr: int, width: int, height: int,
+                               albedo_ptr: int = 0, normal_ptr: int = 0, depth_ptr: int = 0, sigmas=GUIDE_SIGMAS,
+                               out_format: int = RT_OUT_F32, radius: int = PYRAMID_WINDOW[0],
+                               patch: int = PYRAMID_WINDOW[1], k: float = PYRAMID_WINDOW[2],
+                               levels: int = PYRAMID_LEVELS, stream: Optional[int] = None):
+        """Enqueues rt_denoise_pyramid over device buffers on `stream`: as denoise_guided_device."""
+        p = PyramidParams(int(width), int(height), int(out_format), 1, int(radius), int(patch), float(k), int(levels),
+                          0, stream)
+        sa, sn, sz = (float(v) for v in sigmas)
+        g = DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+        _check(self.lib.rt_denoise_pyramid(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr),
+                                           ctypes.c_void_p(stderr_ptr), ctypes.byref(g), ctypes.c_void_p(out_ptr)),
+               "rt_denoise_pyramid")
+
+    def pyramid_stats(self) -> PyramidStats:
+        s = PyramidStats()
+        _check(self.lib.rt_pyramid_last_stats(self.h, ctypes.byref(s)), "rt_pyramid_last_stats")
         return s
 
     def denoise_cross(self, mean_a, mean_b, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
