@@ -110,7 +110,26 @@ int rt_world_material_dielectric(rt_world* w, double ir, int* handle_out);
 int rt_world_material_diffuse_light(rt_world* w, int tex, int* handle_out);
 int rt_world_material_isotropic(rt_world* w, int tex, int* handle_out);
 
-/* Hittables (hittable.rs:30-41, constructors :77-207) -> hittable id >= 0. */
+/* Hittables (hittable.rs:30-41, constructors :77-207) -> hittable id >= 0.
+ * The constructors take every value the reference's take, and a world built from them either
+ * renders what the reference computes for it or is refused with a message before any launch
+ * (the context stays usable):
+ *   a radius < 0 (the hollow-glass idiom)  accepted: hit by |radius|, normals divided by radius
+ *   a moving sphere's shutter (t0, t1)     t0 == t1 or a non-finite value: RT_ERR_INVALID (the centre
+ *                                          divides by t1 - t0); otherwise accepted, also t0 > t1 and
+ *                                          shutters beside [0, 1]; its centre extrapolates to any
+ *                                          ray time, and the boxes cover the build's time range
+ *                                          (RT_BUILD_TIME0 / _TIME1, default [0, 1]); rt_render
+ *                                          and the other passes refuse a camera whose time0 / time1
+ *                                          leave that range (RT_ERR_UNSUPPORTED) when the scene
+ *                                          holds a moving sphere
+ *   rt_world_bvh over a child whose reference bounding box does not bound it (a sphere of
+ *   radius < 0, or a moving sphere whose own shutter does not cover the build's time range,
+ *   not wrapped in a rotate_y, whose box is a hull of corners): the reference culls by that
+ *   box, so its image depends on its hierarchy; rt_world_flatten / rt_ctx_upload_world refuse
+ *   the world with RT_ERR_UNSUPPORTED, naming the node and the child, in every accel mode
+ *   chains of more than 4 translate / rotate_y, and a medium boundary holding instances or
+ *   media: RT_ERR_UNSUPPORTED at flatten, as before. */
 int rt_world_sphere(rt_world* w, int mat, const double center[3], double radius, int* id_out);
 int rt_world_moving_sphere(rt_world* w, int mat, const double c0[3], const double c1[3], double t0, double t1,
                            double radius, int* id_out);
@@ -165,7 +184,12 @@ enum {
     RT_BUILD_FORCE_LEAF = 3,       /* a set this small is always one leaf (2) */
     RT_BUILD_ROOT_LEAF = 4,        /* a whole BVH of at most this many items is one leaf (8) */
     RT_BUILD_SPLIT_BOX_PAIRS = 5,  /* pairs holding a Box, a medium or a BLAS instance split by cost (1) */
-    RT_BUILD_SPLIT_BLAS_PAIRS = 6  /* pairs inside instance BLASes split by cost (1) */
+    RT_BUILD_SPLIT_BLAS_PAIRS = 6, /* pairs inside instance BLASes split by cost (1) */
+    /* not tuning knobs: the ray times [min, max] of the two the node boxes are built for (0 and 1),
+     * any finite value taken as it is; set them to the shutter of the camera the world will be
+     * rendered with when that is not within [0, 1] (rt_scene_soa.time_lo / time_hi) */
+    RT_BUILD_TIME0 = 7,
+    RT_BUILD_TIME1 = 8
 };
 int rt_world_set_build_option(rt_world* w, int key, double value);
 /* Flattens the world into SoA tables owned by the world (valid until the next

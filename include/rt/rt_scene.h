@@ -125,10 +125,19 @@ typedef struct rt_scene_soa {
     const double* perlin_ranvec;   /* [n_perlin][256][3] */
     const int32_t* perlin_perm;    /* [n_perlin][3][256] (x, y, z) */
     const uint8_t* image_data;
+    /* The ray times the node boxes are valid for: every box bounds what the primitive tests
+     * below it accept for a ray time in [time_lo, time_hi] (a moving sphere's centre
+     * extrapolates beyond its own shutter, hittable.rs:556-558). A render whose camera has
+     * time0 or time1 outside is refused (RT_ERR_UNSUPPORTED) when the scene holds a moving
+     * sphere. rt_world_flatten writes [0, 1] unless RT_BUILD_TIME0 / _TIME1 are set; a foreign
+     * host states the range its own boxes cover (left at 0 and 0, a scene with moving spheres
+     * renders only under a camera with time0 = time1 = 0). */
+    double time_lo, time_hi;
 } rt_scene_soa;
 
 /* Acceleration structure the flattener builds. The image does not depend
- * on it (closest hit is independent of the hierarchy); only the traversal cost does.
+ * on it (closest hit is independent of the hierarchy while every box bounds what the tests
+ * below it accept: flatten.cpp's box invariant); only the traversal cost does.
  *   SAH    : full-sweep SAH BVHs over the dissolved reference BvhNodes (default, fastest)
  *   LINEAR : every list scanned in order, as hit_hittables (hittable.rs:31-41) does:
  *            a chain of unbounded nodes over <=31-primitive leaves

@@ -1406,8 +1406,20 @@ int orc_world_texture(orc_world* o, int kind, const double c0[3], const double c
         tl_rng = saved;
         return ow_tex(o, tex_noise(p, scale));
     }
-    default: return -1;
+    default: return -1;   /* TEX_IMAGE takes texels: orc_world_texture_image */
     }
+}
+/* Texture::Image (texture.rs:12-22) over RGB8 texels as stb_image returns them; the world copies
+ * them. No texels (NULL, or a zero size): the texture that answers cyan (texture.rs:48-50). */
+int orc_world_texture_image(orc_world* o, const uint8_t* rgb, int w, int h)
+{
+    if (!o || w < 0 || h < 0) return -1;
+    if (!rgb || w == 0 || h == 0) return ow_tex(o, tex_image(NULL, w, h));
+    const size_t n = (size_t)w * (size_t)h * 3;
+    uint8_t* copy = (uint8_t*)arena_alloc(&o->w.arena, n);
+    if (!copy) return -1;
+    memcpy(copy, rgb, n);
+    return ow_tex(o, tex_image(copy, w, h));
 }
 int orc_world_material(orc_world* o, int kind, int tex, const double albedo[3], double fuzz, double ir)
 {

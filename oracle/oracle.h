@@ -95,6 +95,7 @@ typedef struct orc_world orc_world;
 int orc_world_create(uint64_t scene_seed, orc_world** out);
 void orc_world_destroy(orc_world* w);
 int orc_world_texture(orc_world* w, int kind, const double c0[3], const double c1[3], double scale); /* 0 solid 1 checker 2 noise */
+int orc_world_texture_image(orc_world* w, const uint8_t* rgb, int width, int height);   /* 3 image: RGB8 texels, copied */
 int orc_world_material(orc_world* w, int kind, int tex, const double albedo[3], double fuzz, double ir);
 int orc_world_sphere(orc_world* w, int mat, const double c[3], double r);
 int orc_world_moving_sphere(orc_world* w, int mat, const double c0[3], const double c1[3], double t0, double t1,

@@ -410,6 +410,8 @@ int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_
     rq.acc_sink = sink.acc != nullptr;
     rq.moments = sink.moments != nullptr;
     rq.cam_mag = rtp::camera_magnitude(*cam);
+    rq.cam_time0 = cam->time0;
+    rq.cam_time1 = cam->time1;
     // the plan, and its buffers: an attempt whose trace output (or ring) does not fit the device
     // is planned again without the ring, or under half the bound (this render only: the
     // context's bound stays, so a later render on it uses the memory freed since)

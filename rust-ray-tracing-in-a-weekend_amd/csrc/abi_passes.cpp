@@ -268,6 +268,8 @@ int rt_render_features(rt_ctx* c, const rt_camera* cam, const rt_render_params* 
     rq.s_end = p->spp;
     rq.chunk = chunk;
     rq.cam_mag = rtp::camera_magnitude(*cam);
+    rq.cam_time0 = cam->time0;
+    rq.cam_time1 = cam->time1;
     const rtp::Plan pl = rtp::plan(c->scene, c->dev, opt, rq, rtp::Retry{c->sample_buf_cap, false});
     if (pl.err) return fail(pl.err, pl.err_msg);
 

@@ -112,6 +112,9 @@ int rt_world_moving_sphere(rt_world* w, int mat, const double c0[3], const doubl
 {
     CHECK_WORLD(w, o);
     if (!c0 || !c1 || !w->w.valid_material(mat)) return fail(RT_ERR_INVALID, "bad moving sphere");
+    // MovingSphere::center divides by t1 - t0 (hittable.rs:556-558): no centre, and no box, without it
+    if (!std::isfinite(t0) || !std::isfinite(t1) || t0 == t1)
+        return fail(RT_ERR_INVALID, "moving sphere: t0 and t1 must be finite and different");
     *o = w->w.moving_sphere(mat, vec(c0), vec(c1), t0, t1, r);
     return RT_OK;
 }
@@ -281,6 +284,8 @@ int rt_world_set_build_option(rt_world* w, int key, double v)
     case RT_BUILD_ROOT_LEAF: b.root_leaf = iv; return RT_OK;
     case RT_BUILD_SPLIT_BOX_PAIRS: b.split_box_pairs = iv; return RT_OK;
     case RT_BUILD_SPLIT_BLAS_PAIRS: b.split_blas_pairs = iv; return RT_OK;
+    case RT_BUILD_TIME0: b.time0 = v; return RT_OK;
+    case RT_BUILD_TIME1: b.time1 = v; return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown build option");
     }
 }

@@ -5,7 +5,8 @@
 //   Sphere / MovingSphere / XY,XZ,YZ rects / Box   -> one rt_prim each
 //   BvhNode (reference median BVH, :77-130)        -> dissolved; its leaves join the
 //                                                     enclosing SAH BVH (closest-hit is
-//                                                     independent of the hierarchy)
+//                                                     independent of the hierarchy, see
+//                                                     the box invariant below)
 //   Translate / RotateY chains (:232-244, :386-415) -> rt_instance (<= 4 ops) whose child
 //                                                     is a single prim or its own BLAS
 //   ConstantMedium (:417-473)                       -> RT_PRIM_MEDIUM whose boundary is a
@@ -17,6 +18,18 @@
 // accel (rt_scene.h) picks the hierarchy: SAH (above), LINEAR (every list a chain of
 // unbounded nodes over <=31-prim leaves, in list order: hit_hittables' linear scan), or
 // MEDIAN (the reference's BvhNodes kept node for node, the top-level list a chain).
+//
+// The box invariant. "Closest hit is independent of the hierarchy" holds only while every node
+// box bounds everything the primitive tests below it can accept. The reference's own
+// bounding_box does not give that (a radius < 0 inverts a sphere's box; a moving sphere's box
+// spans its own shutter, while its centre extrapolates to any ray time), so every box here
+// comes from Builder::bound_of: |r|, and a moving sphere's centres over the ray times
+// [time_lo, time_hi] the tables are built for — [0, 1] unless RT_BUILD_TIME0 / _TIME1 say
+// otherwise, recorded in rt_scene_soa; a render whose camera shutter leaves that range is
+// refused (launch_plan.cpp) when the scene holds a moving sphere. The one place the reference
+// culls by its own boxes is a BvhNode (rt_world_bvh): a node with a child whose reference box
+// does not bound it is refused at flatten (RT_ERR_UNSUPPORTED, check_ref_bvhs), in every accel
+// mode, because the reference's image then depends on its hierarchy.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -107,13 +120,132 @@ struct Builder {
         return add_prim(p);
     }
 
+    // ---- the box invariant ---------------------------------------------------------------
+    // Every box the kernel walks bounds what the hit tests below it accept, for every ray time in
+    // [time_lo, time_hi]. World::bounding_box (the reference's, hittable.rs:475-554) does not:
+    // a sphere of radius r < 0 (hit by its |r|, hittable.rs:254-288) gets the inverted box
+    // c - r .. c + r, and a moving sphere the hull of its centres at its own shutter t0, t1 while
+    // MovingSphere::center extrapolates to any ray time (:556-558). The reference's top-level list
+    // is a linear scan and never notices; here the list is a BVH. So the boxes are the product's
+    // own: |r|, and the centres at the two ends of the time range (the centre is linear in time).
+    // For r > 0 and a shutter equal to the range they are the reference's, bit for bit.
+    double time_lo = 0.0, time_hi = 1.0;
+
+    static AABB hull(const AABB& a, const AABB& b)
+    {
+        return AABB{v3(std::fmin(a.minimum.x, b.minimum.x), std::fmin(a.minimum.y, b.minimum.y),
+                       std::fmin(a.minimum.z, b.minimum.z)),
+                    v3(std::fmax(a.maximum.x, b.maximum.x), std::fmax(a.maximum.y, b.maximum.y),
+                       std::fmax(a.maximum.z, b.maximum.z))};
+    }
+
+    AABB bound_of(int hid) const
+    {
+        const HNode& h = w.nodes[hid];
+        switch (h.kind) {
+        case HKind::Sphere: {
+            const double r = std::fabs(h.radius);
+            return AABB{h.c0 - v3(r, r, r), h.c0 + v3(r, r, r)};
+        }
+        case HKind::MovingSphere: {
+            const double r = std::fabs(h.radius);
+            const V3 a = h.c0 + (h.c1 - h.c0) * ((time_lo - h.t0) / (h.t1 - h.t0));   // hittable.rs:556-558
+            const V3 b = h.c0 + (h.c1 - h.c0) * ((time_hi - h.t0) / (h.t1 - h.t0));
+            return hull(AABB{a - v3(r, r, r), a + v3(r, r, r)}, AABB{b - v3(r, r, r), b + v3(r, r, r)});
+        }
+        case HKind::BvhNode: return h.right == h.left ? bound_of(h.left) : hull(bound_of(h.left), bound_of(h.right));
+        case HKind::Translate: {
+            const AABB b = bound_of(h.ptr);
+            return AABB{b.minimum + h.offset, b.maximum + h.offset};
+        }
+        case HKind::RotateY: {   // the eight corners, as hittable.rs:147-199 rotates the child's box
+            const AABB b = bound_of(h.ptr);
+            AABB r{v3(INFINITY, INFINITY, INFINITY), v3(-INFINITY, -INFINITY, -INFINITY)};
+            for (int k = 0; k < 8; ++k) {
+                const double x = (k & 4) ? b.maximum.x : b.minimum.x, y = (k & 2) ? b.maximum.y : b.minimum.y;
+                const double z = (k & 1) ? b.maximum.z : b.minimum.z;
+                const double nx = h.cos_theta * x + h.sin_theta * z, nz = -h.sin_theta * x + h.cos_theta * z;
+                r = hull(r, AABB{v3(nx, y, nz), v3(nx, y, nz)});
+            }
+            return r;
+        }
+        case HKind::ConstantMedium: return bound_of(h.ptr);
+        default: {   // rects and boxes: the reference's box bounds them
+            AABB b;
+            w.bounding_box(hid, 0.0, 1.0, b);
+            return b;
+        }
+        }
+    }
+
+    static const char* kind_name(HKind k)
+    {
+        switch (k) {
+        case HKind::Sphere: return "sphere";
+        case HKind::MovingSphere: return "moving sphere";
+        case HKind::BvhNode: return "bvh node";
+        case HKind::XYRect: case HKind::XZRect: case HKind::YZRect: return "rect";
+        case HKind::Box: return "box";
+        case HKind::Translate: return "translate";
+        case HKind::RotateY: return "rotate_y";
+        case HKind::ConstantMedium: return "constant medium";
+        }
+        return "hittable";
+    }
+
+    // Under an rt_world_bvh node the reference itself culls by its own boxes (hittable.rs:290-306,
+    // aabb.rs:77-103: an inverted box is never hit), so where such a box does not bound its child the
+    // reference's image depends on its hierarchy, which neither a SAH BVH nor a list scan
+    // reproduces. Such a node is refused: every child's reference box must contain the child's bound.
+    int check_ref_bvhs()
+    {
+        std::vector<char> seen(w.nodes.size(), 0);
+        std::vector<int> todo(w.hittables.begin(), w.hittables.end());
+        bool nested = false;
+        while (!todo.empty()) {
+            const int id = todo.back();
+            todo.pop_back();
+            if (!w.valid_hittable(id) || seen[(size_t)id]) continue;
+            seen[(size_t)id] = 1;
+            const HNode& h = w.nodes[id];
+            if (h.kind == HKind::Translate || h.kind == HKind::RotateY || h.kind == HKind::ConstantMedium) todo.push_back(h.ptr);
+            if (h.kind != HKind::BvhNode) continue;
+            for (int c : {h.left, h.right}) {
+                todo.push_back(c);
+                if (!w.valid_hittable(c)) continue;
+                AABB ref;
+                const AABB own = bound_of(c);
+                const bool ok = w.bounding_box(c, 0.0, 1.0, ref) &&
+                                ref.minimum.x <= own.minimum.x && ref.minimum.y <= own.minimum.y && ref.minimum.z <= own.minimum.z &&
+                                ref.maximum.x >= own.maximum.x && ref.maximum.y >= own.maximum.y && ref.maximum.z >= own.maximum.z;
+                // (a child that is a BvhNode itself fails only through a child of its own, named when
+                // the walk reaches it: its reference box is the hull of its children's)
+                if (!ok && w.nodes[c].kind == HKind::BvhNode) {
+                    nested = true;
+                    continue;
+                }
+                if (!ok) {
+                    err = "rt_world_bvh node " + std::to_string(id) + ": the reference's box of its child " + std::to_string(c) +
+                          " (a " + kind_name(w.nodes[c].kind) + ") does not bound what that child's hit test accepts for ray times in [" +
+                          std::to_string(time_lo) + ", " + std::to_string(time_hi) +
+                          "] (a negative radius, or a moving sphere's shutter inside that range); the reference culls by that box";
+                    return RT_ERR_UNSUPPORTED;
+                }
+            }
+        }
+        if (nested) {   // not reached while a BvhNode's box is the hull of its children's
+            err = "an rt_world_bvh node's reference box does not bound its children";
+            return RT_ERR_UNSUPPORTED;
+        }
+        return RT_OK;
+    }
+
     Item item_of(int prim, int hid)
     {
         Item it;
         it.prim = prim;
         it.ref = 0;
-        AABB b;
-        w.bounding_box(hid, 0.0, 1.0, b);
+        const AABB b = bound_of(hid);
         it.lo[0] = b.minimum.x; it.lo[1] = b.minimum.y; it.lo[2] = b.minimum.z;
         it.hi[0] = b.maximum.x; it.hi[1] = b.maximum.y; it.hi[2] = b.maximum.z;
         for (int a = 0; a < 3; ++a) it.c[a] = 0.5 * (it.lo[a] + it.hi[a]);
@@ -193,12 +325,7 @@ struct Builder {
         return it;
     }
 
-    AABB box_of(int hid) const
-    {
-        AABB b;
-        w.bounding_box(hid, 0.0, 1.0, b);
-        return b;
-    }
+    AABB box_of(int hid) const { return bound_of(hid); }
 
     int make_instance(const Ops& ops, int child_kind, int child)
     {
@@ -670,10 +797,19 @@ int flatten(World& w, int accel, std::string& err)
     if (bo.root_leaf >= 0) bld.root_leaf = std::min(31, bo.root_leaf);
     if (bo.split_box_pairs >= 0) bld.split_box_pairs = bo.split_box_pairs != 0;
     if (bo.split_blas_pairs >= 0) bld.split_blas_pairs = bo.split_blas_pairs != 0;
+    // the ray times the boxes are built for (RT_BUILD_TIME0 / _TIME1; launch_plan.cpp refuses a
+    // camera whose shutter leaves them when the scene holds a moving sphere)
+    if (!std::isfinite(bo.time0) || !std::isfinite(bo.time1)) {
+        err = "build time range not finite";
+        return RT_ERR_INVALID;
+    }
+    bld.time_lo = std::min(bo.time0, bo.time1);
+    bld.time_hi = std::max(bo.time0, bo.time1);
+    if (int rc = bld.check_ref_bvhs()) return rc;
     std::vector<Item> top;
     for (int id : w.hittables) {  // M for the f32-slab padding (see to_f32_box)
-        AABB b;
-        if (w.valid_hittable(id) && w.bounding_box(id, 0.0, 1.0, b)) {
+        if (w.valid_hittable(id)) {
+            const AABB b = bld.bound_of(id);
             const double c[6] = {b.minimum.x, b.minimum.y, b.minimum.z, b.maximum.x, b.maximum.y, b.maximum.z};
             for (double v : c)
                 if (std::isfinite(v)) bld.world_extent = std::max(bld.world_extent, std::fabs(v));
@@ -777,6 +913,8 @@ int flatten(World& w, int accel, std::string& err)
     s.accel = accel;
     s.image_bytes = (int64_t)f.image.size();
     s.pad_extent = bld.world_extent;
+    s.time_lo = bld.time_lo;
+    s.time_hi = bld.time_hi;
     s.tlas_depth = tlas_depth;
     s.n_tlas_nodes = n_tlas_nodes;
     s.blas_depth = bld.blas_depth;

@@ -95,6 +95,9 @@ SceneFacts scene_facts(const rtl::Lowered& L, const rt_scene_soa& s)
     f.n_materials = s.n_materials;
     f.n_textures = s.n_textures;
     f.pad_extent = L.pad_extent;
+    f.has_moving = L.has_moving;
+    f.time_lo = L.time_lo;
+    f.time_hi = L.time_hi;
     return f;
 }
 
@@ -128,6 +131,13 @@ Plan plan(const SceneFacts& scene, const DeviceFacts& dev, const Options& opt, c
         e.err_msg = why;
         return e;
     };
+    // a moving sphere's boxes bound it for ray times in the scene's [time_lo, time_hi] only
+    // (flatten.cpp's box invariant), and camera rays carry times between time0 and time1:
+    // outside, a node box could cull a sphere the exact test hits (negated: a NaN is refused too)
+    if (scene.has_moving && !(std::min(rq.cam_time0, rq.cam_time1) >= scene.time_lo &&
+                              std::max(rq.cam_time0, rq.cam_time1) <= scene.time_hi))
+        return unsupported("the camera's time0 / time1 leave the time range the scene's boxes were built for "
+                           "(rt_scene_soa.time_lo / time_hi; RT_BUILD_TIME0 / RT_BUILD_TIME1 before rt_world_flatten)");
     if (rq.moments && pl.f32) return unsupported("adaptive sampling in the f32 mode");
     if (pl.f32 && rq.count_work && variant != rtk::FEAT_SET_SPHERES && variant != rtk::FEAT_SET_FINAL)
         return unsupported("count_work in the f32 mode: the spheres and final-scene variants only");

@@ -36,6 +36,10 @@ struct SceneFacts {   // what the context keeps of an uploaded scene
     int n_blas_bfs = 0, stack_entries = 0, stack16_ok = 0;   // rtl::Lowered's fields of these names
     int n_materials = 0, n_textures = 0;
     double pad_extent = 0.0;
+    // the scene holds a moving sphere, whose boxes bound it for ray times in [time_lo, time_hi]
+    // (rtl::Lowered's fields of these names; rt_scene_soa.time_lo / time_hi)
+    int has_moving = 0;
+    double time_lo = 0.0, time_hi = 1.0;
 };
 SceneFacts scene_facts(const rtl::Lowered& L, const rt_scene_soa& s);
 
@@ -64,6 +68,7 @@ struct Request {
     bool acc_sink = false;      // the sums are added to a caller's accumulator (rt_accum_add)
     bool moments = false;       // an rt_render_adaptive pass: the moments sink
     double cam_mag = 0.0;       // camera_magnitude(camera)
+    double cam_time0 = 0.0, cam_time1 = 1.0;   // the camera's shutter: every ray time lies between them
 };
 // how far from the origin a camera ray can start (the camera and its lens): the slab32 test
 double camera_magnitude(const rt_camera& cam);
@@ -76,8 +81,8 @@ struct Retry {
 
 // ---- the plan -------------------------------------------------------------------------------------
 struct Plan {
-    int err = RT_OK;            // RT_ERR_UNSUPPORTED (and why) for the two f32 cases no kernel serves:
-    const char* err_msg = "";   // nothing below is set then
+    int err = RT_OK;            // RT_ERR_UNSUPPORTED (and why) for the two f32 cases no kernel serves and for a
+    const char* err_msg = "";   // camera shutter outside the scene's time range: nothing below is set then
     // the launch options
     uint32_t features = 0;      // scene features | extra features
     uint32_t variant = 0;       // rtk::variant_features of them

@@ -471,6 +471,10 @@ int lower(const rt_scene_soa& s, bool hoist, Lowered& L, std::string& err)
     for (int i = 0; i < s.n_materials; ++i)
         if (s.materials[i].kind == RT_MAT_DIFFUSE_LIGHT) L.has_lights = 1;
     L.pad_extent = s.pad_extent > 0.0 && std::isfinite(s.pad_extent) ? s.pad_extent : 0.0;
+    for (int i = 0; i < s.n_prims; ++i)
+        if (s.prims[i].kind == RT_PRIM_MOVING_SPHERE) L.has_moving = 1;
+    L.time_lo = s.time_lo;
+    L.time_hi = s.time_hi;
     return RT_OK;
 }
 

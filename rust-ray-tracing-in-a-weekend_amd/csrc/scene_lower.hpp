@@ -22,6 +22,8 @@ struct Lowered {
     float pre_lo[3] = {}, pre_hi[3] = {};
     int has_lights = 0, has_spheres = 0;
     double pad_extent = 0.0;
+    int has_moving = 0;                       // any RT_PRIM_MOVING_SPHERE: its boxes hold for ray times in
+    double time_lo = 0.0, time_hi = 0.0;      //   [time_lo, time_hi] only (rt_scene_soa's fields)
 };
 
 // Both return RT_OK, or an RT_ERR_* code with its message in err.

@@ -100,6 +100,7 @@ struct BuildOptions {
     int root_leaf = -1;         // RT_BUILD_ROOT_LEAF: a whole BVH of at most this many items is one leaf
     int split_box_pairs = -1;   // RT_BUILD_SPLIT_BOX_PAIRS: pairs holding a Box / medium / BLAS instance split by cost
     int split_blas_pairs = -1;  // RT_BUILD_SPLIT_BLAS_PAIRS: pairs inside instance BLASes split by cost
+    double time0 = 0.0, time1 = 1.0;   // RT_BUILD_TIME0 / _TIME1: the ray times the boxes are built for
 };
 
 class World {

@@ -59,6 +59,8 @@ RT_BUILD_FORCE_LEAF = 3
 RT_BUILD_ROOT_LEAF = 4
 RT_BUILD_SPLIT_BOX_PAIRS = 5
 RT_BUILD_SPLIT_BLAS_PAIRS = 6
+RT_BUILD_TIME0 = 7              # the ray times the node boxes are built for (default 0 and 1): set them to
+RT_BUILD_TIME1 = 8              # the camera's shutter when that is not within [0, 1]
 
 # every symbol include/rt/rt_abi.h declares
 EXPORTED = [
@@ -127,7 +129,7 @@ class SceneSoA(ctypes.Structure):
                 ("prims", ctypes.c_void_p), ("prim_refs", ctypes.c_void_p), ("nodes", ctypes.c_void_p),
                 ("instances", ctypes.c_void_p), ("materials", ctypes.c_void_p), ("textures", ctypes.c_void_p),
                 ("perlin_ranvec", ctypes.c_void_p), ("perlin_perm", ctypes.c_void_p),
-                ("image_data", ctypes.c_void_p)]
+                ("image_data", ctypes.c_void_p), ("time_lo", ctypes.c_double), ("time_hi", ctypes.c_double)]
 
 
 class RenderParams(ctypes.Structure):

@@ -233,6 +233,28 @@ void image_world(World& w, int which)
 }
 
 // ---- edits of the flattened tables -----------------------------------------------------
+// What the reference's bounding_box does not bound (flatten.cpp's box invariant): spheres of
+// negative radius, alone, concentric and under a rotate_y, and moving spheres whose shutter does
+// not cover the ray times [0, 1], among enough spheres for the top level to have nodes; under
+// an rt_world_bvh node instead when under_bvh.
+void unbounded_by_reference(World& w, bool under_bvh)
+{
+    const int wh = white(w), glass = w.dielectric(1.5);
+    std::vector<int> ids;
+    for (int i = 0; i < 12; ++i) ids.push_back(w.sphere(i % 2 ? wh : glass, v3((double)i, 0.5, 0.0), 0.4));
+    ids.push_back(w.sphere(glass, v3(14.0, 3.0, 0.0), -0.9));
+    ids.push_back(w.sphere(glass, v3(3.0, 2.0, 1.0), 0.6));
+    ids.push_back(w.sphere(glass, v3(3.0, 2.0, 1.0), -0.5));
+    for (int i = 0; i < 6; ++i)
+        ids.push_back(w.moving_sphere(wh, v3((double)i, 0.5, 2.0), v3((double)i, 1.5, 2.0), i % 2 ? 0.25 : 2.0, i % 2 ? 0.75 : 3.0, 0.3));
+    if (under_bvh) {
+        w.push(bvh(w, ids));
+    } else {
+        for (int id : ids) w.push(id);
+        w.push(w.translate(w.rotate_y(w.sphere(wh, v3(0.5, 0.5, 0.0), -0.4), 135.0), v3(-3.0, 0.0, 0.0)));
+    }
+}
+
 bool spheres_only(const rt_scene_soa& s, int ref)
 {
     if (ref >= 0) return spheres_only(s, s.nodes[ref].child[0]) && spheres_only(s, s.nodes[ref].child[1]);
@@ -418,6 +440,23 @@ int main()
         if (big_leaves) w.build.force_leaf = 16, w.build.max_leaf = 31;
         sphere_field(w, n);
         dump_world((std::string(big_leaves ? "sphere_field_leaf31_" : "sphere_field_") + std::to_string(n)).c_str(), w);
+    }
+    // the box invariant: negative radii and shutters inside / beside [0, 1] are lowered with the
+    // product's own boxes; under an rt_world_bvh node they are refused at flatten in every mode;
+    // built for the ray times [-1, 4] the shutter [2, 3] is still inside the range
+    for (int accel = 0; accel < 3; ++accel) {
+        World w(6), v(6);
+        unbounded_by_reference(w, false);
+        dump_world((std::string("unbounded_by_reference_") + accel_name[accel]).c_str(), w, accel);
+        unbounded_by_reference(v, true);
+        dump_world((std::string("unbounded_by_reference_under_bvh_") + accel_name[accel]).c_str(), v, accel);
+    }
+    {
+        World w(6);
+        w.build.time0 = -1.0;
+        w.build.time1 = 4.0;
+        unbounded_by_reference(w, false);
+        dump_world("unbounded_by_reference_times_m1_4", w);
     }
     return 0;
 }

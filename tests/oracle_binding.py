@@ -57,6 +57,7 @@ def lib() -> ctypes.CDLL:
     l.orc_camera.restype = ctypes.c_int
     P, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     for name, args in {"orc_world_create": [ctypes.c_uint64, P], "orc_world_texture": [P, I, P, P, D],
+                       "orc_world_texture_image": [P, P, I, I],
                        "orc_world_material": [P, I, I, P, D, D], "orc_world_sphere": [P, I, P, D],
                        "orc_world_moving_sphere": [P, I, P, P, D, D, D], "orc_world_rect": [P, I, I, D, D, D, D, D],
                        "orc_world_box": [P, P, P, I], "orc_world_translate": [P, I, P], "orc_world_rotate_y": [P, I, D],
@@ -187,6 +188,13 @@ class OracleWorld:
     def solid(self, r, g, b): return self._id(lib().orc_world_texture(self.h, 0, self._d3((r, g, b)), self._d3((0, 0, 0)), 0.0))
     def checker(self, even, odd): return self._id(lib().orc_world_texture(self.h, 1, self._d3(even), self._d3(odd), 0.0))
     def noise(self, scale): return self._id(lib().orc_world_texture(self.h, 2, self._d3((0, 0, 0)), self._d3((0, 0, 0)), scale))
+
+    def image(self, rgb):
+        """Texture::Image over an (h, w, 3) uint8 array; the oracle copies the texels."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        assert rgb.ndim == 3 and rgb.shape[2] == 3, rgb.shape
+        return self._id(lib().orc_world_texture_image(self.h, rgb.ctypes.data, rgb.shape[1], rgb.shape[0]))
+
     def _mat(self, kind, tex=0, albedo=(0, 0, 0), fuzz=0.0, ir=0.0):
         return self._id(lib().orc_world_material(self.h, kind, tex, self._d3(albedo), fuzz, ir))
     def lambertian(self, tex): return self._mat(0, tex)
@@ -236,7 +244,7 @@ class TwinWorld:
     so hittable arguments are translated through a product-id -> oracle-id table."""
 
     HITTABLE_ARGS = {"translate": (0,), "rotate_y": (0,), "constant_medium": (0,), "push": (0,)}
-    SAME_IDS = {"solid", "checker", "noise", "lambertian", "metal", "dielectric", "diffuse_light", "isotropic"}
+    SAME_IDS = {"solid", "checker", "noise", "image", "lambertian", "metal", "dielectric", "diffuse_light", "isotropic"}
 
     def __init__(self, rt, scene_seed: int = 1):
         self.product = rt.World(scene_seed)

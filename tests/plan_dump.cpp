@@ -3,7 +3,9 @@
 // it builds the scene, flattens and lowers it, forms the request as rt_render / rt_accum_add do
 // and prints one JSON line per attempt: the case's own bound with the ring allowed ("primary": 1),
 // then that bound halved down to 1 MiB, each with the ring allowed and ruled out — the attempts
-// run_range's out-of-memory loop can reach. Links scene_model.cpp, flatten.cpp, scene_lower.cpp
+// run_range's out-of-memory loop can reach. A case may give the camera's shutter ("cam_time0",
+// "cam_time1") and the build's time range ("build_time0", "build_time1"); without them both are
+// [0, 1]. Links scene_model.cpp, flatten.cpp, scene_lower.cpp
 // and launch_plan.cpp and nothing from HIP; built with ASan and UBSan by tests/test_launch_plan.py.
 #include <algorithm>
 #include <cstdint>
@@ -13,6 +15,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 
 #include "rt/rt_abi.h"
 #include "launch_plan.hpp"
@@ -32,6 +35,15 @@ long long geti(const std::string& line, const char* key)
         std::exit(2);
     }
     return std::strtoll(inputs.c_str() + at + k.size(), nullptr, 10);
+}
+
+// the number after "key": among the case's inputs, or dflt when the case does not give it
+double getd(const std::string& line, const char* key, double dflt)
+{
+    const std::string inputs = line.substr(0, line.find("\"expect\""));
+    const std::string k = std::string("\"") + key + "\":";
+    const size_t at = inputs.find(k);
+    return at == std::string::npos ? dflt : std::strtod(inputs.c_str() + at + k.size(), nullptr);
 }
 
 std::string gets(const std::string& line, const char* key)
@@ -58,8 +70,8 @@ struct Scene {
 void print_plan(const std::string& name, const rtp::Plan& pl, const rtp::SceneFacts& f, const rtp::Retry& retry, int chunk,
                 bool primary)
 {
-    std::printf("{\"case\": \"%s\", \"primary\": %d, \"bound\": %zu, \"ring_allowed\": %d, \"err\": %d, ", name.c_str(),
-                primary ? 1 : 0, retry.buf_cap, retry.ring_allowed ? 1 : 0, pl.err);
+    std::printf("{\"case\": \"%s\", \"primary\": %d, \"bound\": %zu, \"ring_allowed\": %d, \"err\": %d, \"err_msg\": \"%s\", ",
+                name.c_str(), primary ? 1 : 0, retry.buf_cap, retry.ring_allowed ? 1 : 0, pl.err, pl.err_msg);
     // rt_stats' fields of these names, as abi.cpp's write_stats derives them
     std::printf("\"schedule\": %d, \"n_batches\": %d, \"trace_buf_bytes\": %zu, \"ring_bytes\": %zu, \"overlapped\": %d, "
                 "\"lds_nodes\": %d, \"slab32\": %d, \"lds_stack\": %d, \"variant_features\": %u, \"precision\": %d, "
@@ -91,17 +103,22 @@ int main(int argc, char** argv)
     dev.lds_per_cu = (size_t)geti(line, "lds_per_cu");
     dev.lds_per_block = (size_t)geti(line, "lds_per_block");
 
-    std::map<int, std::unique_ptr<Scene>> scenes;
+    // a scene per (id, build time range): "build_time0" / "build_time1" (optional) are
+    // RT_BUILD_TIME0 / _TIME1, "cam_time0" / "cam_time1" (optional) the camera's shutter
+    std::map<std::tuple<int, double, double>, std::unique_ptr<Scene>> scenes;
     while (std::getline(in, line)) {
         if (line.empty()) continue;
-        const int id = (int)geti(line, "scene");
+        const int sid = (int)geti(line, "scene");
+        const auto id = std::make_tuple(sid, getd(line, "build_time0", 0.0), getd(line, "build_time1", 1.0));
         if (!scenes.count(id)) {   // rt_ctx_upload_world: flatten (SAH), lower (hoist on)
             auto sc = std::make_unique<Scene>();
             std::string err;
             rtl::Lowered L;
-            if (rtw::build_scene(sc->world, id, gradient(), 4, 2) || rtw::flatten(sc->world, RT_ACCEL_SAH, err) ||
+            sc->world.build.time0 = std::get<1>(id);
+            sc->world.build.time1 = std::get<2>(id);
+            if (rtw::build_scene(sc->world, sid, gradient(), 4, 2) || rtw::flatten(sc->world, RT_ACCEL_SAH, err) ||
                 rtl::lower(sc->world.flat.soa, true, L, err)) {
-                std::fprintf(stderr, "plan_dump: scene %d: %s\n", id, err.c_str());
+                std::fprintf(stderr, "plan_dump: scene %d: %s\n", sid, err.c_str());
                 return 1;
             }
             sc->facts = rtp::scene_facts(L, sc->world.flat.soa);
@@ -119,9 +136,10 @@ int main(int argc, char** argv)
         p.tile_shard = (int)geti(line, "tile_shard");
         if (rtp::bad_geometry(&p)) return 1;
         rtw::Preset pre;
-        if (!rtw::scene_preset(id, pre)) return 1;
+        if (!rtw::scene_preset(sid, pre)) return 1;
         rt_camera cam = rtw::camera_new(pre.look_from, pre.look_at, rtw::v3(0.0, 1.0, 0.0), pre.vfov,
-                                        (double)p.width / (double)p.height, 0.1, 10.0, 0.0, 1.0);   // rt_scene_camera
+                                        (double)p.width / (double)p.height, 0.1, 10.0, getd(line, "cam_time0", 0.0),
+                                        getd(line, "cam_time1", 1.0));   // rt_scene_camera, or the case's shutter
         if (geti(line, "cam_far")) cam.origin[0] = 1e9, cam.origin[1] = 0.0, cam.origin[2] = 0.0;
 
         rtp::Options opt;
@@ -144,6 +162,8 @@ int main(int argc, char** argv)
         rq.chunk = p.spp_chunk > 0 ? (accum ? p.spp_chunk : std::min(p.spp_chunk, p.spp)) : rtp::auto_chunk(p.spp);
         rq.acc_sink = accum;
         rq.cam_mag = rtp::camera_magnitude(cam);
+        rq.cam_time0 = cam.time0;
+        rq.cam_time1 = cam.time1;
 
         const std::string name = gets(line, "case");
         const size_t bound = (size_t)geti(line, "buf_bytes");

@@ -90,25 +90,31 @@ def test_nested_world_accel_modes_and_f32(rt, renderer):
     assert np.all(np.isfinite(f32)) and abs(float(f32.mean()) / float(f64.mean()) - 1.0) < 0.1
 
 
-def _moving_world(rt, t0, t1):
+def _moving_world(rt, t0, t1, n=5):
     tw = ob.TwinWorld(rt, 3)
     white = tw.lambertian(tw.checker((0.2, 0.3, 0.1), (0.9, 0.9, 0.9)))
     red = tw.lambertian(tw.solid(0.7, 0.1, 0.1))
     metal = tw.metal((0.8, 0.8, 0.9), 0.2)
     tw.push(tw.sphere(white, (0.0, -1000.0, 0.0), 1000.0))
-    for i in range(5):
-        c0 = (-2.0 + i, 0.3, 0.2 * i)
+    for i in range(n):
+        c0 = (-2.0 + i % 5, 0.3, 0.2 * (i % 5) + 1.2 * (i // 5))
         tw.push(tw.moving_sphere(red if i % 2 else metal, c0, (c0[0], c0[1] + 0.4, c0[2]), t0, t1, 0.3))
     tw.push(tw.moving_sphere(red, (0.5, 1.2, -1.0), (0.9, 1.2, -1.0), 0.0, 1.0, 0.4))
     return tw
 
 
-@pytest.mark.parametrize("t0,t1,feat", [(0.0, 1.0, 0), (0.25, 0.75, 4095), (-1.0, 2.0, 4095)])
+@pytest.mark.parametrize("t0,t1,feat", [(0.0, 1.0, 0), (0.25, 0.75, 4095), (-1.0, 2.0, 4095),
+                                        pytest.param(0.25, 0.75, (4095, 12), id="0.25-0.75-4095-12_spheres")])
 def test_moving_sphere_shutters_match_oracle(rt, renderer, t0, t1, feat):
     """MovingSphere::center (hittable.rs:556-558) for any shutter: [0, 1] shutters (every
     reference scene) take the spheres variant, which loads no per-primitive shutter flag;
-    another shutter selects FEAT_SHUTTER (the all-features variant) and its division."""
-    tw = _moving_world(rt, t0, t1)
+    another shutter selects FEAT_SHUTTER (the all-features variant) and its division.
+    The worlds of 7 items are one root leaf; the one of 12 moving spheres (14 items) has node
+    boxes, which must bound the centres the shutter extrapolates to under the camera's [0, 1]."""
+    feat, n = feat if isinstance(feat, tuple) else (feat, 5)
+    tw = _moving_world(rt, t0, t1, n)
+    if n > 8:
+        assert tw.product.flatten().n_tlas_nodes > 0
     got, ref = _render_both(rt, renderer, tw, 40, 24, 6, (6.0, 2.0, 5.0), (0.0, 0.5, 0.0), (0.7, 0.8, 1.0))
     assert renderer.stats().variant_features == feat
     assert_parity(got, ref, f"moving spheres, shutter [{t0}, {t1}]")

@@ -139,6 +139,37 @@ def test_every_attempt_upholds_the_plans_invariants(attempts):
     assert n > 4 * len(cases)
 
 
+def test_a_camera_shutter_outside_the_scenes_time_range_is_refused(plan_dump, tmp_path):
+    """A moving sphere's boxes bound it for the ray times the tables were built for (flatten.cpp's
+    box invariant; [0, 1] unless RT_BUILD_TIME0 / _TIME1 say otherwise). The plan refuses a camera
+    whose time0 / time1 leave that range, before anything is allocated or launched, on a scene that
+    holds a moving sphere (the random scene) and on no other (the Cornell box)."""
+    dev, _ = golden()
+    frame = dict(width=64, height=48, spp=4)
+    cases = {
+        "inside": dict(scene=0, cam_time0=0.25, cam_time1=0.75),
+        "equal": dict(scene=0, cam_time0=0.0, cam_time1=1.0),
+        "reversed": dict(scene=0, cam_time0=1.0, cam_time1=0.0),
+        "late": dict(scene=0, cam_time0=0.0, cam_time1=1.5),
+        "early": dict(scene=0, cam_time0=-0.001, cam_time1=1.0),
+        "disjoint": dict(scene=0, cam_time0=2.0, cam_time1=3.0),
+        "built_for_it": dict(scene=0, cam_time0=-0.5, cam_time1=1.5, build_time0=-0.5, build_time1=1.5),
+        "built_reversed": dict(scene=0, cam_time0=-0.5, cam_time1=1.5, build_time0=1.5, build_time1=-0.5),
+        "built_narrower": dict(scene=0, cam_time0=0.0, cam_time1=1.0, build_time0=0.25, build_time1=0.75),
+        "nothing_moves": dict(scene=5, cam_time0=-3.0, cam_time1=7.0),
+    }
+    path = tmp_path / "cases.json"
+    path.write_text("\n".join([json.dumps(dev)] + [json.dumps(dict(DEFAULTS, case=k, **frame, **v)) for k, v in cases.items()]) + "\n")
+    out = plan_dump(str(path))
+    assert {a["case"] for a in out} == set(cases)
+    refused = {"late", "early", "disjoint", "built_narrower"}
+    for a in out:   # every attempt of the out-of-memory loop, not only the first
+        if a["case"] in refused:
+            assert a["err"] == -3 and "time range" in a["err_msg"] and a["n_batches"] == 0 and a["trace_buf_bytes"] == 0, a
+        else:
+            assert a["err"] == 0 and a["err_msg"] == "" and a["n_batches"] >= 1, a
+
+
 def test_hidden_plan_fields_follow_the_stated_rules(plan_dump, attempts, tmp_path):
     """What rt_stats does not show, against values worked out by hand from the rules as
     launch_plan.cpp states them."""

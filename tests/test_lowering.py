@@ -54,6 +54,14 @@ def test_golden_agrees_with_what_the_project_states():
     c = {w["case"]: w for w in map(json.loads, open(GOLDEN))}
     refused = {"refused_nonprimitive": "an instance BVH holds a non-primitive", "refused_cycle": "cycle in an instance BVH",
                "refused_nonprimitive_then_cycle": "an instance BVH holds a non-primitive", "refused_bad_node": "bad node"}
+    # refused by the flattener itself, in every accel mode: an rt_world_bvh node over children the
+    # reference's boxes do not bound (flatten.cpp's box invariant); the message names node and child
+    at_flatten = ["unbounded_by_reference_under_bvh_" + a for a in ("sah", "linear", "median")]
+    for name in at_flatten:
+        w = c.pop(name)
+        assert w["flatten_rc"] == -3 and w["err"].startswith("rt_world_bvh node ") and " its child " in w["err"], name
+    # ... and lowered with the product's own boxes everywhere else (nodes only under SAH)
+    assert c["unbounded_by_reference_sah"]["n_tlas_nodes"] > 0 and c["unbounded_by_reference_times_m1_4"]["n_tlas_nodes"] > 0
     for name, w in c.items():   # validate's refusals carry the messages tests/test_abi.py asserts on
         assert (w["rc"] != 0 and w["err"] == refused[name]) if name in refused else w["rc"] == 0, name
     # random scene: the spheres variant with 16-bit stack entries, its ground sphere hoisted
