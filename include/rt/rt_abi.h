@@ -41,6 +41,8 @@
  *                             weights, with the error left read off their difference
  *   rt_denoise_pyramid        (new) rt_denoise_guided run at several scales of the frame, the coarse
  *                             scales supplying the low frequencies its window cannot see
+ *   rt_adaptive_state_*       (new) rt_render_adaptive's accumulators kept between calls: the frame
+ *                             tightened, previewed, checkpointed, or steered by a caller's error map
  *
  * Threading: a context is bound to one device and is used by one host thread at
  * a time. Worlds are plain host objects.
@@ -552,6 +554,155 @@ int rt_render_adaptive_halves(rt_ctx* ctx, const rt_camera* cam, const rt_render
  * (either may be NULL). For callers with accumulators of their own, and for tests. */
 int rt_adaptive_tile_errors_host(const double* sums, const double* q, const uint32_t* tile_spp, int width,
                                  int height, double* tile_error_out, double* stderr_out);
+
+/* ---- a resumable, refinable adaptive frame (additive to ABI v6: new symbols only) ----------------
+ * rt_render_adaptive allocates its accumulators, runs to its threshold, resolves and frees them.
+ * An rt_adaptive_state owns them between calls instead: S, Q, the half sums (with_halves),
+ * tile_spp, tile_error and a tile order. It is advanced by rt_render_adaptive's trace passes and
+ * moments kernel, so it can be tightened to a lower threshold, previewed between launches,
+ * checkpointed, and steered by an error map of the caller's (a filter's error estimate reduced to
+ * tiles, say). A tile's history depends on no other tile: every draw is keyed by (pixel, sample), a
+ * tile only sits at counts of the schedule below, and it stops at the first of them where E_t <=
+ * threshold.
+ *
+ * Create binds the camera, the context's current scene upload and p's width, height, max_depth,
+ * background, render_seed and chunk (p->spp_chunk, or rt_render's automatic chunk for p->spp when
+ * that is 0); the shard fields must be unset as for rt_render_adaptive; p->spp >= 1 only chooses
+ * the automatic chunk. min_r and step_r are ap->min_spp (>= 2) and ap->step_spp (>= 1) rounded up
+ * to the chunk; ap->threshold is ignored. The accumulators are zero and every tile has count 0.
+ * RT_PREC_F32 contexts: RT_ERR_UNSUPPORTED, at create and at advance. A scene upload on the
+ * context after create makes every later advance fail with RT_ERR_INVALID; the state can still be
+ * resolved, read and destroyed. Destroy the state before its context (as an rt_accum).
+ *
+ * Schedule:  next(n) = min(spp_cap, n == 0 ? min_r : n + step_r).
+ * Stops:     stops(E, threshold) = threshold > 0 and E <= threshold (rt_render_adaptive's
+ *            predicate: a threshold <= 0 stops no tile, nor does a NaN E).
+ * Active:    tile t with count n_t is active if n_t < spp_cap and (n_t == 0 or not
+ *            stops(E_t, threshold)).
+ * Advance:   until no tile is active, or max_launches groups have run:
+ *              n* = the lowest count among the active tiles;
+ *              the group = every active tile with count n*, in ascending raster index;
+ *              samples [n*, next(n*)) of the group are traced as one tile shard under the state's
+ *              own tile order [every other tile | the group], on the POOL schedule's per-sample
+ *              buffer, exactly as a pass of rt_render_adaptive (buffer batches carry the sums
+ *              across), and reduced by its moments kernel, which writes the group's tile_spp =
+ *              next(n*) and E_t;
+ *              one small record is read back (one synchronization per group).
+ *            Every launch closes its last chunk: nothing is open between calls. *active_left =
+ *            the active tiles after the call under this call's threshold and cap (may be NULL).
+ *            The call is synchronous. On a fresh state run to completion the groups are exactly
+ *            rt_render_adaptive's passes with the tiles in the same order (a stable partition of
+ *            raster order stays ascending).
+ * Ragged caps: a launch that ends at an spp_cap that is no multiple of the chunk closes a partial
+ *            chunk. From then on an advance with a larger spp_cap is RT_ERR_INVALID before
+ *            anything is launched (continuing would split that chunk's sum); the state remembers
+ *            the cap on the host (and in its checkpoint). A cap below some tiles' counts is fine:
+ *            those tiles are not active.
+ * A caller's error map (tile_error_in not NULL, one f64 per raster tile; a device pointer if
+ *            error_on_device): one round. The selected set is fixed at entry: the tiles with
+ *            n_t < spp_cap and not stops(tile_error_in[t], threshold). Every selected tile gets
+ *            exactly one step, to next(n_t); groups are formed by count, lowest first. A stepped
+ *            tile's E_t is refreshed by the moments kernel, the others keep theirs.
+ *            max_launches must be 0 and no tile may be at count 0 (RT_ERR_INVALID).
+ *            *active_left = 0: the round always completes.
+ * Resolve:   rt_render_adaptive's resolve on the state's sums: mean (out_format), tile_spp,
+ *            tile_error, stderr_map and (halves) the two half means, to host pointers or (on_device)
+ *            device pointers; synchronous, on the context's stream. RT_ERR_INVALID while a tile is
+ *            at count 0, and for halves on a state created without them. It may be called between
+ *            any two advances: a preview holds each tile at its own count.
+ *
+ * Consequences ("equals": every output bit for bit — the mean in both formats, tile_spp,
+ * tile_error, stderr_map, mean_a and mean_b):
+ *  1. A fresh state advanced to completion with (thr, cap) and resolved equals
+ *     rt_render_adaptive(_halves) with spp = cap and the same chunk, min, step and threshold.
+ *  2. advance(thr1), ..., advance(thrk) with decreasing thresholds equals one advance(thrk): the
+ *     first scheduled count with E_t <= thrk cannot come before the first with E_t <= thr1.
+ *  3. Any split of an advance by max_launches equals the unsplit advance.
+ *  4. Raising the cap from c1 to c2 equals one run at cap c2, when c1 is on the schedule
+ *     min_r + j step_r and a multiple of the chunk.
+ *  5. get, set into a second state of the same create parameters, then continuing, equals
+ *     continuing the first.
+ *  6. After any sequence of calls a tile at count n holds rt_render's pixels at spp = n, same chunk.
+ *
+ * A regroup kernel (one 1024-thread workgroup, no atomics) chooses each group on the device; its
+ * rule is stated once more on the host, rt_adaptive_next_group_host. rt_last_stats follows
+ * rt_render_adaptive's convention for an advance; rt_adaptive_last_stats is not touched. The
+ * context's tile order, schedule, options and deal-order cache are not touched. One GPU. */
+typedef struct rt_adaptive_state rt_adaptive_state;
+int rt_adaptive_state_create(rt_ctx* ctx, const rt_camera* cam, const rt_render_params* p,
+                             const rt_adaptive_params* ap, int with_halves, rt_adaptive_state** out);
+void rt_adaptive_state_destroy(rt_adaptive_state* st);
+
+typedef struct rt_adaptive_advance_params {
+    double threshold;             /* as rt_adaptive_params.threshold (NaN: RT_ERR_INVALID) */
+    int32_t spp_cap;              /* >= 2: the most samples a tile may hold after this call */
+    int32_t max_launches;         /* 0: until no tile is active; k > 0: at most k groups */
+    int32_t error_on_device;      /* tile_error_in is a device pointer */
+    int32_t reserved0;
+    const double* tile_error_in;  /* optional, one value per raster tile: a caller's error map */
+    void* stream;                 /* NULL: the context's stream */
+} rt_adaptive_advance_params;
+int rt_adaptive_state_advance(rt_adaptive_state* st, const rt_adaptive_advance_params* ap, int32_t* active_left);
+
+/* out->mean is required, the others optional (rt_adaptive_out); halves NULL, or both members set. */
+int rt_adaptive_state_resolve(rt_adaptive_state* st, int out_format, int on_device, const rt_adaptive_out* out,
+                              const rt_adaptive_halves* halves);
+
+/* A checkpoint on the host. The header names what a restore must match and carries the host side
+ * of the state; the arrays are the frame-layout accumulators (nothing is open between calls). */
+typedef struct rt_adaptive_state_header {
+    int32_t width, height;
+    int32_t spp_chunk, min_spp, step_spp;   /* as rounded: min_r, step_r */
+    int32_t with_halves;
+    int32_t ragged_cap;                     /* 0, or the cap at which a partial chunk was closed */
+    int32_t reserved0;
+    uint64_t groups_total, samples_total;   /* as rt_adaptive_state_stats */
+} rt_adaptive_state_header;
+typedef struct rt_adaptive_state_data {
+    double* sums;         /* height x width x 3: S */
+    double* q;            /* height x width: Q */
+    uint32_t* tile_spp;   /* per raster tile */
+    double* tile_error;   /* per raster tile */
+    double* sum_a;        /* height x width x 3 each; with_halves only, else ignored */
+    double* sum_b;
+} rt_adaptive_state_data;
+/* header (required) and, if data is not NULL, every array of it (all required; sum_a / sum_b only
+ * with halves). Host pointers. */
+int rt_adaptive_state_get(rt_adaptive_state* st, rt_adaptive_state_header* header, const rt_adaptive_state_data* data);
+/* Restores a checkpoint: width, height, spp_chunk, min_spp, step_spp and with_halves must be the
+ * state's own; every count is 0 or >= 2, and a multiple of the chunk or the header's ragged_cap
+ * (RT_ERR_INVALID otherwise, the state unchanged). */
+int rt_adaptive_state_set(rt_adaptive_state* st, const rt_adaptive_state_header* header,
+                          const rt_adaptive_state_data* data);
+
+typedef struct rt_adaptive_state_stats {
+    int32_t groups;             /* groups traced by the last advance */
+    int32_t active_left;        /* active tiles after it, under its threshold and cap */
+    int32_t min_count, max_count;   /* the lowest and the highest tile count now */
+    int32_t spp_chunk, min_spp, step_spp;   /* as rounded */
+    int32_t tiles;              /* tiles of the frame */
+    uint64_t samples_traced;    /* by the last advance: 64 x tiles x samples, summed over its groups */
+    uint64_t groups_total, samples_total;   /* since create (or as restored) */
+    double trace_ms;            /* the last advance, HIP events summed over its groups: the trace kernels, */
+    double moments_ms;          /*   the moments reductions, */
+    double classify_ms;         /*   the regroup launches (with their readback) */
+} rt_adaptive_state_stats;
+int rt_adaptive_state_last_stats(rt_adaptive_state* st, rt_adaptive_state_stats* out);
+
+/* The selection rule on the host, no device needed: the next group of a frame with the given
+ * counts. Give tile_error (the threshold decides, as in an advance) or selected (one byte per tile,
+ * nonzero = selected, as in a caller's-map round: threshold is ignored), not both. min_r and step_r
+ * are multiples of the chunk already. group_out (may be NULL; room for n_tiles) receives the
+ * group's raster indices in ascending order. No active tile: n_group = 0, n_star = n_next = 0. */
+typedef struct rt_adaptive_group {
+    int64_t n_group;    /* tiles of the group */
+    int64_t n_active;   /* active tiles, the group's included */
+    int32_t n_star;     /* the group's count */
+    int32_t n_next;     /* next(n_star) */
+} rt_adaptive_group;
+int rt_adaptive_next_group_host(const uint32_t* tile_spp, const double* tile_error, const uint8_t* selected,
+                                int64_t n_tiles, double threshold, int32_t spp_cap, int32_t min_r, int32_t step_r,
+                                uint32_t* group_out, rt_adaptive_group* out);
 
 /* ---- variance-guided NL-means denoiser (additive to ABI v6: new symbols only) ------------------
  * A post-filter for rt_render_adaptive's frame that needs only the colour and the per-pixel

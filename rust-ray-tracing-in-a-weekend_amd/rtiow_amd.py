@@ -87,6 +87,9 @@ EXPORTED = [
     "rt_denoise_atrous", "rt_denoise_atrous_host", "rt_atrous_last_stats",
     "rt_denoise_pyramid", "rt_denoise_pyramid_host", "rt_pyramid_last_stats",
     "rt_render_adaptive_halves", "rt_denoise_cross", "rt_denoise_cross_host", "rt_cross_last_stats",
+    "rt_adaptive_state_create", "rt_adaptive_state_destroy", "rt_adaptive_state_advance",
+    "rt_adaptive_state_resolve", "rt_adaptive_state_get", "rt_adaptive_state_set",
+    "rt_adaptive_state_last_stats", "rt_adaptive_next_group_host",
 ]
 
 # int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_total)
@@ -198,6 +201,48 @@ class AdaptiveStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AdaptiveAdvanceParams(ctypes.Structure):
+    """rt_adaptive_advance_params."""
+    _fields_ = [("threshold", ctypes.c_double), ("spp_cap", ctypes.c_int32), ("max_launches", ctypes.c_int32),
+                ("error_on_device", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("tile_error_in", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+
+
+class AdaptiveStateHeader(ctypes.Structure):
+    """rt_adaptive_state_header: what a checkpoint must match, and the host side of the state."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("spp_chunk", ctypes.c_int32),
+                ("min_spp", ctypes.c_int32), ("step_spp", ctypes.c_int32), ("with_halves", ctypes.c_int32),
+                ("ragged_cap", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("groups_total", ctypes.c_uint64), ("samples_total", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AdaptiveStateData(ctypes.Structure):
+    """rt_adaptive_state_data: a checkpoint's arrays (host pointers)."""
+    _fields_ = [("sums", ctypes.c_void_p), ("q", ctypes.c_void_p), ("tile_spp", ctypes.c_void_p),
+                ("tile_error", ctypes.c_void_p), ("sum_a", ctypes.c_void_p), ("sum_b", ctypes.c_void_p)]
+
+
+class AdaptiveStateStats(ctypes.Structure):
+    """rt_adaptive_state_stats: the last advance of a state, and its totals."""
+    _fields_ = [("groups", ctypes.c_int32), ("active_left", ctypes.c_int32), ("min_count", ctypes.c_int32),
+                ("max_count", ctypes.c_int32), ("spp_chunk", ctypes.c_int32), ("min_spp", ctypes.c_int32),
+                ("step_spp", ctypes.c_int32), ("tiles", ctypes.c_int32), ("samples_traced", ctypes.c_uint64),
+                ("groups_total", ctypes.c_uint64), ("samples_total", ctypes.c_uint64),
+                ("trace_ms", ctypes.c_double), ("moments_ms", ctypes.c_double), ("classify_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AdaptiveGroup(ctypes.Structure):
+    """rt_adaptive_group: what rt_adaptive_next_group_host decides."""
+    _fields_ = [("n_group", ctypes.c_int64), ("n_active", ctypes.c_int64), ("n_star", ctypes.c_int32),
+                ("n_next", ctypes.c_int32)]
 
 
 class DenoiseParams(ctypes.Structure):
@@ -402,6 +447,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_denoise_cross": ([P, ctypes.POINTER(CrossParams), P, P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
         "rt_denoise_cross_host": ([ctypes.POINTER(CrossParams), P, P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
         "rt_cross_last_stats": ([P, ctypes.POINTER(CrossStats)], I),
+        "rt_adaptive_state_create": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
+                                      ctypes.POINTER(AdaptiveParams), I, ctypes.POINTER(P)], I),
+        "rt_adaptive_state_destroy": ([P], None),
+        "rt_adaptive_state_advance": ([P, ctypes.POINTER(AdaptiveAdvanceParams), ctypes.POINTER(ctypes.c_int32)], I),
+        "rt_adaptive_state_resolve": ([P, I, I, ctypes.POINTER(AdaptiveOut), ctypes.POINTER(AdaptiveHalves)], I),
+        "rt_adaptive_state_get": ([P, ctypes.POINTER(AdaptiveStateHeader), ctypes.POINTER(AdaptiveStateData)], I),
+        "rt_adaptive_state_set": ([P, ctypes.POINTER(AdaptiveStateHeader), ctypes.POINTER(AdaptiveStateData)], I),
+        "rt_adaptive_state_last_stats": ([P, ctypes.POINTER(AdaptiveStateStats)], I),
+        "rt_adaptive_next_group_host": ([P, P, P, ctypes.c_int64, D, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P,
+                                         ctypes.POINTER(AdaptiveGroup)], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name, None)
@@ -716,6 +771,27 @@ def adaptive_tile_errors_host(sums, q, tile_spp, width: int, height: int):
     _check(lib.rt_adaptive_tile_errors_host(s.ctypes.data, qq.ctypes.data, n.ctypes.data, width, height,
                                             err.ctypes.data, se.ctypes.data), "rt_adaptive_tile_errors_host")
     return err, se
+
+
+def adaptive_next_group_host(tile_spp, threshold: float, spp_cap: int, min_r: int, step_r: int, tile_error=None,
+                             selected=None):
+    """rt_adaptive_next_group_host: the selection rule of an rt_adaptive_state (rt_abi.h) on the host,
+    no device needed. Give tile_error (the threshold decides) or selected (a mask, nonzero =
+    selected). Returns (group: raster indices ascending, n_star, n_next, n_active)."""
+    lib = load_library()
+    n = np.ascontiguousarray(tile_spp, dtype=np.uint32).reshape(-1)
+    err = None if tile_error is None else np.ascontiguousarray(tile_error, dtype=np.float64).reshape(-1)
+    sel = None if selected is None else np.ascontiguousarray(np.asarray(selected) != 0, dtype=np.uint8).reshape(-1)
+    for a in (err, sel):
+        if a is not None and a.size != n.size:
+            raise RTError(f"adaptive_next_group_host: {a.size} values for {n.size} tiles")
+    group = np.empty(max(n.size, 1), dtype=np.uint32)
+    g = AdaptiveGroup()
+    _check(lib.rt_adaptive_next_group_host(n.ctypes.data, None if err is None else err.ctypes.data,
+                                           None if sel is None else sel.ctypes.data, n.size, float(threshold),
+                                           int(spp_cap), int(min_r), int(step_r), group.ctypes.data, ctypes.byref(g)),
+           "rt_adaptive_next_group_host")
+    return group[:g.n_group].copy(), g.n_star, g.n_next, g.n_active
 
 
 def _denoise_args(mean, se, radius, patch, k):
@@ -1209,6 +1285,11 @@ class Renderer:
         _check(self.lib.rt_adaptive_last_stats(self.h, ctypes.byref(s)), "rt_adaptive_last_stats")
         return s
 
+    def adaptive_state(self, camera: Camera, params: RenderParams, min_spp: int, step_spp: int,
+                       halves: bool = False) -> "AdaptiveState":
+        """rt_adaptive_state_create: render_adaptive's accumulators kept between calls (rt_abi.h)."""
+        return AdaptiveState(self, camera, params, min_spp, step_spp, halves)
+
     def accumulator(self, params: RenderParams) -> "Accumulator":
         return Accumulator(self, params)
 
@@ -1446,6 +1527,121 @@ class Accumulator:
         _check(self.lib.rt_accum_resolve(self.r.h, self.h, divisor, out_format, 0, out.ctypes.data),
                "rt_accum_resolve")
         return out
+
+
+class AdaptiveState:
+    """A resumable, refinable adaptive frame (rt_adaptive_state_*, rt_abi.h): advance it to a
+    threshold and a cap, resolve it between any two advances, checkpoint and restore it, or steer
+    one round by a per-tile error map. Close it before its renderer."""
+
+    def __init__(self, renderer: Renderer, camera: Camera, params: RenderParams, min_spp: int, step_spp: int,
+                 halves: bool = False):
+        self.r, self.lib = renderer, renderer.lib
+        self.width, self.height, self.halves = params.width, params.height, bool(halves)
+        self.tiles_y, self.tiles_x = (self.height + 7) // 8, (self.width + 7) // 8
+        ap = AdaptiveParams(int(min_spp), int(step_spp), 0.0)
+        h = ctypes.c_void_p()
+        _check(self.lib.rt_adaptive_state_create(renderer.h, ctypes.byref(camera), ctypes.byref(params),
+                                                 ctypes.byref(ap), int(self.halves), ctypes.byref(h)),
+               "rt_adaptive_state_create")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            if self.r.h:   # (a state outlived by its context is not touched: rt_abi.h's lifetime rule)
+                self.lib.rt_adaptive_state_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def advance(self, threshold: float, spp_cap: int, max_launches: int = 0, tile_error=None,
+                tile_error_ptr: int = 0, stream: Optional[int] = None) -> int:
+        """rt_adaptive_state_advance. tile_error: a caller's error map on the host, one value per
+        raster tile; tile_error_ptr: the same as a device pointer. Returns the active tiles left."""
+        ap = AdaptiveAdvanceParams()
+        ap.threshold, ap.spp_cap, ap.max_launches = float(threshold), int(spp_cap), int(max_launches)
+        ap.stream = stream
+        err = None
+        if tile_error is not None:
+            err = np.ascontiguousarray(tile_error, dtype=np.float64).reshape(-1)
+            if err.size != self.tiles_x * self.tiles_y:
+                raise RTError(f"advance: {err.size} errors for {self.tiles_x * self.tiles_y} tiles")
+            ap.tile_error_in = err.ctypes.data
+        elif tile_error_ptr:
+            ap.tile_error_in, ap.error_on_device = tile_error_ptr, 1
+        left = ctypes.c_int32()
+        _check(self.lib.rt_adaptive_state_advance(self.h, ctypes.byref(ap), ctypes.byref(left)),
+               "rt_adaptive_state_advance")
+        return left.value
+
+    def resolve(self, out_format: int = RT_OUT_F32):
+        """rt_adaptive_state_resolve to the host: render_adaptive's (mean, tile_spp, tile_error,
+        stderr_map), and with halves render_adaptive_halves' (..., mean_a, mean_b)."""
+        W, H = self.width, self.height
+        dt = np.float64 if out_format == RT_OUT_F64 else np.float32
+        mean = np.empty((H, W, 3), dtype=dt)
+        tile_spp = np.zeros((self.tiles_y, self.tiles_x), dtype=np.uint32)
+        tile_error = np.zeros((self.tiles_y, self.tiles_x), dtype=np.float64)
+        se = np.empty((H, W), dtype=np.float64)
+        out = AdaptiveOut(mean.ctypes.data, tile_spp.ctypes.data, tile_error.ctypes.data, se.ctypes.data)
+        if not self.halves:
+            _check(self.lib.rt_adaptive_state_resolve(self.h, out_format, 0, ctypes.byref(out), None),
+                   "rt_adaptive_state_resolve")
+            return mean, tile_spp, tile_error, se
+        mean_a, mean_b = np.empty((H, W, 3), dtype=dt), np.empty((H, W, 3), dtype=dt)
+        hv = AdaptiveHalves(mean_a.ctypes.data, mean_b.ctypes.data)
+        _check(self.lib.rt_adaptive_state_resolve(self.h, out_format, 0, ctypes.byref(out), ctypes.byref(hv)),
+               "rt_adaptive_state_resolve")
+        return mean, tile_spp, tile_error, se, mean_a, mean_b
+
+    def resolve_device(self, out_format: int, mean_ptr: int, stderr_ptr: int = 0, tile_spp_ptr: int = 0,
+                       tile_error_ptr: int = 0, mean_a_ptr: int = 0, mean_b_ptr: int = 0):
+        """rt_adaptive_state_resolve into device buffers (e.g. torch tensors' data_ptr()); the half
+        means when either of their pointers is given. The call itself is synchronous."""
+        out = AdaptiveOut(mean_ptr, tile_spp_ptr or None, tile_error_ptr or None, stderr_ptr or None)
+        hv = AdaptiveHalves(mean_a_ptr or None, mean_b_ptr or None) if (mean_a_ptr or mean_b_ptr) else None
+        _check(self.lib.rt_adaptive_state_resolve(self.h, out_format, 1, ctypes.byref(out),
+                                                  ctypes.byref(hv) if hv is not None else None),
+               "rt_adaptive_state_resolve")
+
+    def checkpoint(self):
+        """(header, arrays): rt_adaptive_state_get's header and a dict of S, Q, tile_spp, tile_error
+        (and S_a, S_b with halves) — what restore takes."""
+        W, H = self.width, self.height
+        arrays = dict(sums=np.empty((H, W, 3)), q=np.empty((H, W)),
+                      tile_spp=np.empty((self.tiles_y, self.tiles_x), dtype=np.uint32),
+                      tile_error=np.empty((self.tiles_y, self.tiles_x)))
+        if self.halves:
+            arrays.update(sum_a=np.empty((H, W, 3)), sum_b=np.empty((H, W, 3)))
+        hdr = AdaptiveStateHeader()
+        data = AdaptiveStateData(**{k: v.ctypes.data for k, v in arrays.items()})
+        _check(self.lib.rt_adaptive_state_get(self.h, ctypes.byref(hdr), ctypes.byref(data)), "rt_adaptive_state_get")
+        return hdr, arrays
+
+    def restore(self, header: AdaptiveStateHeader, arrays: dict):
+        W, H = self.width, self.height
+        shapes = dict(sums=(H, W, 3), q=(H, W), tile_spp=(self.tiles_y, self.tiles_x),
+                      tile_error=(self.tiles_y, self.tiles_x))
+        if self.halves:
+            shapes.update(sum_a=(H, W, 3), sum_b=(H, W, 3))
+        keep = {}
+        for k, shape in shapes.items():
+            if k not in arrays:
+                raise RTError(f"restore: no {k}")
+            keep[k] = np.ascontiguousarray(arrays[k], dtype=np.uint32 if k == "tile_spp" else np.float64)
+            if keep[k].shape != shape:
+                raise RTError(f"restore: {k} is {keep[k].shape}, the state's is {shape}")
+        data = AdaptiveStateData(**{k: v.ctypes.data for k, v in keep.items()})
+        _check(self.lib.rt_adaptive_state_set(self.h, ctypes.byref(header), ctypes.byref(data)), "rt_adaptive_state_set")
+
+    def stats(self) -> AdaptiveStateStats:
+        s = AdaptiveStateStats()
+        _check(self.lib.rt_adaptive_state_last_stats(self.h, ctypes.byref(s)), "rt_adaptive_state_last_stats")
+        return s
 
 
 def render_scene(scene_id: int, width: int, height: int, spp: int, max_depth: int = 50, scene_seed: int = 1,

@@ -1,0 +1,264 @@
+"""The host side of rt_adaptive_state (include/rt/rt_abi.h), no device:
+
+* rt_adaptive_next_group_host against the numpy rule of tests/adaptive_state_reference.py;
+* tile independence: the host rule driven one group per call over oracle-derived samples lands
+  every tile where adaptive_reference.simulate's one-shot run at the last threshold does;
+* csrc/adaptive_schedule.cpp (the schedule, the ragged-cap rule, every parameter check) through
+  tests/adaptive_schedule_main.cpp, built with ASan and UBSan as a stand-alone program;
+* the ctypes mirrors of the new structs against gcc's offsets.
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import adaptive_reference as ar
+from tests import adaptive_state_reference as asr
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "rust-ray-tracing-in-a-weekend_amd", "csrc")
+CLANG = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+         "-ffp-contract=off"]
+
+SPP, MIN, STEP, CHUNK = 96, 16, 16, 16
+# (scene, W, H, chain of (threshold, cap), the one-shot counts the issue recorded at each stage)
+CHAINS = [
+    (0, 40, 24, [(0.06, 96), (0.029, 96), (0.02, 96)], [[16, 32, 48], [16, 32, 64, 80, 96], [16, 32, 48, 80, 96]]),
+    (0, 36, 20, [(0.030, 96), (0.02, 96)], [[16, 48, 64, 96], [16, 32, 96]]),
+    (4, 40, 24, [(0.06, 96), (0.045, 96), (0.029, 96)], [[16, 48, 96], [16, 80, 96], [16, 96]]),
+    (0, 40, 24, [(0.029, 48), (0.029, 96)], [[16, 32, 48], [16, 32, 64, 80, 96]]),
+]
+
+
+def _random_frame(rng, n_tiles, cap_hint):
+    tile_spp = rng.choice([0, 16, 16, 32, 32, 48, 64, 80, 96], size=n_tiles).astype(np.uint32)
+    err = rng.uniform(0.0, 0.1, size=n_tiles)
+    kind = rng.integers(0, 12, size=n_tiles)
+    err[kind == 0] = np.nan
+    err[kind == 1] = np.inf
+    err[kind == 2] = 0.0
+    return tile_spp, err
+
+
+@pytest.mark.parametrize("n_tiles", [1, 15, 63, 64, 65, 1089, 5000])
+def test_next_group_host_matches_numpy(rt, n_tiles):
+    """Seeded random counts (0 included) and errors (NaN, +inf and 0 included); thresholds <= 0, in
+    range and +inf; caps below, at and above the counts; error and mask selection. The group, n*,
+    next(n*) and the active count must be the numpy rule's exactly."""
+    rng = np.random.default_rng(1000 + n_tiles)
+    seen_groups = 0
+    for trial in range(6):
+        tile_spp, err = _random_frame(rng, n_tiles, 96)
+        mask = rng.integers(0, 2, size=n_tiles)
+        if trial == 4:
+            tile_spp[:] = 0          # a fresh frame: the group is every tile
+        if trial == 5:
+            err[:] = 0.001           # nothing active under a positive threshold once sampled
+            tile_spp[tile_spp == 0] = 16
+        for thr in (-1.0, 0.0, 0.03, 0.05, float("inf")):
+            for cap in (2, 16, 40, 48, 96, 100, 200):
+                for sel in (None, mask):
+                    ref = asr.next_group(tile_spp, thr, cap, MIN, STEP, tile_error=None if sel is not None else err,
+                                         selected=sel)
+                    got = rt.adaptive_next_group_host(tile_spp, thr, cap, MIN, STEP,
+                                                      tile_error=None if sel is not None else err, selected=sel)
+                    assert np.array_equal(got[0], ref[0]), (trial, thr, cap, sel is not None)
+                    assert tuple(got[1:]) == tuple(ref[1:]), (trial, thr, cap, sel is not None, got[1:], ref[1:])
+                    assert np.all(np.diff(got[0].astype(np.int64)) > 0)
+                    seen_groups += got[0].size > 0
+    assert seen_groups > 50
+
+
+def test_next_group_host_errors(rt):
+    n, e = np.array([16, 32], dtype=np.uint32), np.array([0.1, 0.2])
+    rt.adaptive_next_group_host(n, 0.05, 96, MIN, STEP, tile_error=e)
+    for kw in (dict(), dict(tile_error=e, selected=[1, 0])):
+        with pytest.raises(rt.RTError, match="RT_ERR_INVALID"):
+            rt.adaptive_next_group_host(n, 0.05, 96, MIN, STEP, **kw)
+    for thr, cap, mn, st in ((float("nan"), 96, MIN, STEP), (0.05, 1, MIN, STEP), (0.05, 96, 1, STEP), (0.05, 96, MIN, 0)):
+        with pytest.raises(rt.RTError, match="RT_ERR_INVALID"):
+            rt.adaptive_next_group_host(n, thr, cap, mn, st, tile_error=e)
+
+
+@pytest.mark.parametrize("scene,W,H,chain,recorded", CHAINS)
+def test_tile_independence_on_oracle_samples(rt, scene, W, H, chain, recorded):
+    """The library's host rule, one group per call, over the numpy moments and criterion of the
+    oracle's samples: after each stage of the chain every tile sits where simulate's one-shot run
+    at that stage's threshold and cap puts it. Every E_t compared in a staged run is compared in
+    one of the one-shot runs, whose margins (>= 0.5 %) therefore bound the staged ones."""
+    samples = ar.oracle_samples(scene, W, H, SPP)
+    ty, tx = (H + 7) // 8, (W + 7) // 8
+    tile_spp = np.zeros(ty * tx, dtype=np.uint32)
+    E = np.zeros(ty * tx)
+    E_at = {}
+    for (thr, cap), counts in zip(chain, recorded):
+        exp_spp, _, _, _, _, tested = ar.simulate(samples, W, H, cap, MIN, STEP, thr)
+        margin = np.min(np.abs(tested / thr - 1.0))
+        print(f"one-shot {thr} cap {cap}: counts {sorted(set(exp_spp.reshape(-1).tolist()))}, margin {margin:.4f}")
+        assert margin >= 0.005
+        assert sorted(set(exp_spp.reshape(-1).tolist())) == counts
+        calls = 0
+        while True:
+            group, n_star, n_next, n_active = rt.adaptive_next_group_host(tile_spp, thr, cap, MIN, STEP, tile_error=E)
+            if group.size == 0:
+                assert n_active == 0
+                break
+            assert (tile_spp[group] == n_star).all() and n_next == min(cap, n_star + STEP if n_star else MIN)
+            if n_next not in E_at:
+                S, Q = ar.moments(samples[:n_next])
+                E_at[n_next] = ar.criterion(S, Q, np.full((ty, tx), n_next), W, H)[1].reshape(-1)
+            tile_spp[group] = n_next
+            E[group] = E_at[n_next][group]
+            calls += 1
+            assert calls <= 64
+        assert np.array_equal(tile_spp.reshape(ty, tx), exp_spp), thr
+
+
+@pytest.fixture(scope="module")
+def schedule_main(tmp_path_factory):
+    """Builds tests/adaptive_schedule_main.cpp over csrc/adaptive_schedule.cpp (no HIP); returns
+    run(lines) -> its output lines."""
+    d = tmp_path_factory.mktemp("adaptive_schedule")
+    exe = str(d / "adaptive_schedule_main")
+    b = subprocess.run([CLANG, *FLAGS, "-I" + os.path.join(REPO, "include"), "-I" + CSRC,
+                        os.path.join(REPO, "tests", "adaptive_schedule_main.cpp"),
+                        os.path.join(CSRC, "adaptive_schedule.cpp"), "-o", exe], capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-4000:]
+    count = [0]
+
+    def run(lines):
+        count[0] += 1
+        case = d / f"case{count[0]}.txt"
+        case.write_text("\n".join(lines) + "\n")
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
+                   UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+        r = subprocess.run([exe, str(case)], capture_output=True, text=True, env=env, timeout=120)
+        report = r.stdout + r.stderr
+        assert "Sanitizer" not in report and "runtime error" not in report, report[-4000:]
+        assert r.returncode == 0, report[-4000:]
+        out = r.stdout.splitlines()
+        assert len(out) == len(lines), report[-4000:]
+        return out
+    return run
+
+
+def test_schedule_and_rounding(schedule_main):
+    out = schedule_main(["next 0 96 16 16", "next 16 96 16 16", "next 80 96 16 32", "next 0 10 16 16", "next 32 40 16 16",
+                         "next 2147483632 2147483647 16 2147483600",
+                         "round 6 4", "round 8 4", "round 1 16", "round 2147483647 16",
+                         "ragged 0 96 16", "ragged 0 40 16", "ragged 40 32 16", "ragged 40 20 16"])
+    assert out == ["16", "32", "96", "10", "40", "2147483647", "8", "8", "16", "2147483632", "0", "40", "40", "20"]
+
+
+def test_create_checks(schedule_main):
+    """W H spp spp_chunk row_begin row_stride row_block tile_shard max_depth min_spp step_spp."""
+    ok = "40 24 96 16 0 1 0 0 50 16 16"
+    cases = {
+        ok: "ok 16 16 16",
+        "40 24 96 0 0 1 0 0 50 6 3": "ok 6 6 6",            # the automatic chunk for spp 96 is 6
+        "40 24 20 0 0 0 1 0 50 16 4": "ok 2 16 4",          # row_stride 0 and row_block 1 are "unset"
+        "40 24 96 4 0 1 0 0 50 6 9": "ok 4 8 12",
+        "40 24 96 16 1 1 0 0 50 16 16": "err",              # shard fields
+        "40 24 96 16 0 2 0 0 50 16 16": "err",
+        "40 24 96 16 0 1 8 0 50 16 16": "err",
+        "40 24 96 16 0 1 0 1 50 16 16": "err",
+        "40 24 96 16 0 1 0 0 50 1 16": "err",               # min_spp < 2
+        "40 24 96 16 0 1 0 0 50 16 0": "err",               # step_spp < 1
+        "1 24 96 16 0 1 0 0 50 16 16": "err",               # geometry
+        "40 24 96 -1 0 1 0 0 50 16 16": "err",
+        "40 24 96 16 0 1 0 0 -1 16 16": "err",
+        "40 24 0 0 0 1 0 0 50 16 16": "err",                # no spp to choose the automatic chunk from
+        "40 24 96 16 0 1 0 0 50 2000000000 16": "err",
+    }
+    out = schedule_main(["create " + c for c in cases])
+    for (case, want), got in zip(cases.items(), out):
+        assert got == want if want.startswith("ok") else got.startswith("err "), (case, got)
+
+
+def test_advance_checks_and_the_ragged_cap_rule(schedule_main):
+    """threshold spp_cap max_launches has_map ragged_cap any_zero."""
+    cases = {
+        "0.02 96 0 0 0 1": True, "0 96 3 0 0 0": True, "-1 2 0 0 0 0": True, "inf 96 0 0 0 0": True,
+        "nan 96 0 0 0 0": False,        # NaN threshold
+        "0.02 1 0 0 0 0": False,        # spp_cap < 2
+        "0.02 96 -1 0 0 0": False,      # max_launches < 0
+        "0.02 40 0 0 40 0": True,       # at the ragged cap
+        "0.02 32 0 0 40 0": True,       # below it: those tiles are simply not active
+        "0.02 41 0 0 40 0": False,      # above it: would split the partial chunk's sum
+        "0.02 96 0 0 40 0": False,
+        "0.5 96 0 1 0 0": True,         # a caller's map
+        "0.5 96 1 1 0 0": False,        #   with max_launches
+        "0.5 96 0 1 0 1": False,        #   on a state with a tile at 0
+        "0.5 96 0 1 40 0": False,       #   above a ragged cap
+    }
+    out = schedule_main(["advance " + c for c in cases])
+    for (case, ok), got in zip(cases.items(), out):
+        assert (got == "ok") if ok else got.startswith("err "), (case, got)
+
+
+def test_restore_checks(schedule_main):
+    """header (W H chunk min step halves ragged), the state's (W H chunk min step halves), counts."""
+    st = "40 24 16 16 16 1"
+    cases = {
+        f"40 24 16 16 16 1 0  {st}  4 16 32 96 0": True,
+        f"40 24 16 16 16 1 40  {st}  3 16 40 32": True,     # a count at the ragged cap
+        f"40 24 16 16 16 1 0  {st}  3 16 40 32": False,     # off the chunk grid, no ragged cap
+        f"40 24 16 16 16 1 40  {st}  2 16 41": False,
+        f"40 24 16 16 16 1 0  {st}  2 16 1": False,
+        f"40 24 16 16 16 1 32  {st}  1 16": False,          # a ragged cap on the grid
+        f"40 24 16 16 16 1 -1  {st}  1 16": False,
+        f"36 24 16 16 16 1 0  {st}  1 16": False,           # another geometry
+        f"40 20 16 16 16 1 0  {st}  1 16": False,
+        f"40 24 8 16 16 1 0  {st}  1 16": False,            # another chunk, min, step, halves
+        f"40 24 16 32 16 1 0  {st}  1 16": False,
+        f"40 24 16 16 32 1 0  {st}  1 16": False,
+        f"40 24 16 16 16 0 0  {st}  1 16": False,
+    }
+    out = schedule_main(["restore " + c for c in cases])
+    for (case, ok), got in zip(cases.items(), out):
+        assert (got == "ok") if ok else got.startswith("err "), (case, got)
+
+
+def test_stand_alone_rule_matches_numpy(schedule_main):
+    """The same rule through the sanitized stand-alone build (the library's copy is tested above)."""
+    rng = np.random.default_rng(7)
+    lines, refs = [], []
+    for n_tiles in (1, 63, 65, 1089):
+        tile_spp, err = _random_frame(rng, n_tiles, 96)
+        mask = rng.integers(0, 2, size=n_tiles)
+        for thr, cap, use_mask in ((0.03, 96, 0), (0.0, 48, 0), (float("inf"), 96, 0), (0.03, 40, 1)):
+            vals = mask if use_mask else err
+            body = " ".join(f"{int(s)} {v!r}" for s, v in zip(tile_spp.tolist(), vals.tolist()))
+            lines.append(f"group {thr!r} {cap} {MIN} {STEP} {use_mask} {n_tiles} {body}")
+            refs.append(asr.next_group(tile_spp, thr, cap, MIN, STEP, tile_error=None if use_mask else err,
+                                       selected=mask if use_mask else None))
+    for got, (g, n_star, n_next, n_active) in zip(schedule_main(lines), refs):
+        assert [int(x) for x in got.split()] == [g.size, n_active, n_star, n_next] + g.tolist()
+
+
+def test_ctypes_structs_match_the_c_header(rt, tmp_path):
+    structs = {"rt_adaptive_advance_params": rt.AdaptiveAdvanceParams, "rt_adaptive_state_header": rt.AdaptiveStateHeader,
+               "rt_adaptive_state_data": rt.AdaptiveStateData, "rt_adaptive_state_stats": rt.AdaptiveStateStats,
+               "rt_adaptive_group": rt.AdaptiveGroup}
+    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "rt/rt_abi.h"', "int main(void) {"]
+    for cname, py in structs.items():
+        src.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
+        for f, _ in py._fields_:
+            src.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
+    src.append("return 0; }")
+    c = tmp_path / "layout.c"
+    c.write_text("\n".join(src))
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-I" + os.path.join(REPO, "include"), str(c), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n")
+    n = 0
+    for line in filter(None, out):
+        cname, field, val = line.split()
+        py = structs[cname]
+        got = ctypes.sizeof(py) if field == "size" else getattr(py, field).offset
+        assert got == int(val), (cname, field, got, int(val))
+        n += 1
+    assert n == sum(len(py._fields_) + 1 for py in structs.values())
