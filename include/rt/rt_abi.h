@@ -483,10 +483,12 @@ int rt_render_progressive(rt_ctx* ctx, const rt_camera* cam, const rt_render_par
  * order); Q uses the same association.
  *
  * Each pass renders the active tiles as one tile shard under a tile order private to the call
- * ([stopped tiles | active tiles]; the context's own order, rt_ctx_set_tile_order, is not touched)
- * on the POOL schedule's per-sample buffer, whatever the context is set to; buffer batches
+ * ([every other tile | the active tiles]; the context's own order, rt_ctx_set_tile_order, is not
+ * touched) on the POOL schedule's per-sample buffer, whatever the context is set to; buffer batches
  * (RT_OPT_TRACE_BUF_BYTES) carry the sums across. A moments kernel reduces the records into
- * frame-layout S and Q and the per-tile error, and a compact kernel re-deals the tiles.
+ * frame-layout S and Q and the per-tile error, and a regroup kernel re-deals the tiles: the one an
+ * rt_adaptive_state (below) chooses its groups with, the call being a fresh state advanced once to
+ * (threshold, p->spp) and resolved.
  * p: the shard fields (row_begin, row_stride other than 0 / 1, row_block > 1, tile_shard) must be
  * unset (RT_ERR_INVALID); count_work is ignored; p->spp >= 2. RT_PREC_F32 contexts:
  * RT_ERR_UNSUPPORTED. One GPU. */
@@ -520,7 +522,7 @@ typedef struct rt_adaptive_stats {
     uint64_t samples_uniform;   /* width x height x p->spp: what rt_render traces for the frame */
     double trace_ms;            /* HIP events, summed over passes: the trace kernels, */
     double moments_ms;          /*   the moments reductions, */
-    double classify_ms;         /*   the compact launches (with their readback) */
+    double classify_ms;         /*   the regroup launches between and after the passes (with their readbacks) */
 } rt_adaptive_stats;
 int rt_adaptive_last_stats(rt_ctx* ctx, rt_adaptive_stats* out);
 

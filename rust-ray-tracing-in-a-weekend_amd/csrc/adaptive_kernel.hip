@@ -1,6 +1,7 @@
 // adaptive_kernel.hip — the kernels of tile-adaptive sampling (rt_render_adaptive): the moments
-// reduction over a pass's per-sample records, the classify / compact step that re-deals the tiles
-// between passes, and the resolve. The criterion itself is adaptive_criterion.hpp.
+// reduction over a pass's per-sample records and the resolve. The criterion itself is
+// adaptive_criterion.hpp; the regroup step that re-deals the tiles between passes is
+// adaptive_state_kernel.hip's.
 #include "adaptive_criterion.hpp"
 #include "trace_kernel.hpp"
 
@@ -209,75 +210,6 @@ __global__ void __launch_bounds__(64 * kMomentWaves) adaptive_moments(const doub
     }
 }
 
-// One workgroup rewrites the tile order after a pass as [stopped tiles | active tiles]: positions
-// below n_stopped are copied, the active ones after them are split by the stop rule, each part in
-// its old order. Ranks come from ballots and popcounts within a wave and a prefix over the
-// workgroup's wave counts in LDS, so the new order is a function of the tile errors alone.
-// counts[0] = tiles stopped so far, counts[1] = tiles still active.
-constexpr int kCompactThreads = 1024;
-__global__ void __launch_bounds__(kCompactThreads) adaptive_compact(const uint32_t* __restrict__ order_in,
-                                                                    uint32_t* __restrict__ order_out,
-                                                                    const double* __restrict__ tile_error,
-                                                                    int n_tiles, int n_stopped, double threshold,
-                                                                    int at_max, uint32_t* __restrict__ counts)
-{
-    constexpr int kWaves = kCompactThreads / 64;
-    __shared__ unsigned w_stop[kWaves], w_keep[kWaves];
-    __shared__ unsigned total_stop;
-    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const unsigned long long below = lane ? ~0ULL >> (64 - lane) : 0ULL;   // the lanes before this one
-    for (int i = tid; i < n_stopped; i += kCompactThreads) order_out[i] = order_in[i];
-
-    // the tiles this pass stops
-    unsigned mine = 0;
-    for (int p0 = n_stopped; p0 < n_tiles; p0 += kCompactThreads) {
-        const int p = p0 + tid;
-        const bool stop = p < n_tiles && (at_max || (threshold > 0.0 && tile_error[order_in[p]] <= threshold));
-        mine += (unsigned)__popcll(__ballot(stop));
-    }
-    if (lane == 0) w_stop[w] = mine;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned s = 0;
-        for (int i = 0; i < kWaves; ++i) s += w_stop[i];
-        total_stop = s;
-    }
-    __syncthreads();
-    const unsigned new_stop = total_stop;
-
-    unsigned base_stop = (unsigned)n_stopped, base_keep = (unsigned)n_stopped + new_stop;
-    for (int p0 = n_stopped; p0 < n_tiles; p0 += kCompactThreads) {
-        const int p = p0 + tid;
-        const bool valid = p < n_tiles;
-        const unsigned tile = valid ? order_in[p] : 0u;
-        const bool stop = valid && (at_max || (threshold > 0.0 && tile_error[tile] <= threshold));
-        const unsigned long long bs = __ballot(stop), bk = __ballot(valid && !stop);
-        __syncthreads();   // the previous round's counts are read
-        if (lane == 0) {
-            w_stop[w] = (unsigned)__popcll(bs);
-            w_keep[w] = (unsigned)__popcll(bk);
-        }
-        __syncthreads();
-        unsigned before_stop = 0, before_keep = 0, round_stop = 0, round_keep = 0;
-        for (int i = 0; i < kWaves; ++i) {
-            if (i < w) {
-                before_stop += w_stop[i];
-                before_keep += w_keep[i];
-            }
-            round_stop += w_stop[i];
-            round_keep += w_keep[i];
-        }
-        if (stop) order_out[base_stop + before_stop + (unsigned)__popcll(bs & below)] = tile;
-        else if (valid) order_out[base_keep + before_keep + (unsigned)__popcll(bk & below)] = tile;
-        base_stop += round_stop;
-        base_keep += round_keep;
-    }
-    if (tid == 0) {
-        counts[0] = (unsigned)n_stopped + new_stop;
-        counts[1] = (unsigned)n_tiles - (unsigned)n_stopped - new_stop;
-    }
-}
-
 // mean = sum * (1 / the tile's sample count), as rt_render writes it, and (se_map not null) the
 // standard error of each pixel's luminance mean. One thread per pixel of the frame.
 template <typename T>
@@ -331,16 +263,6 @@ __global__ void __launch_bounds__(256) adaptive_resolve_halves(const double* __r
         mean_a[3 * i + c] = (T)(sum_a[3 * i + c] * sa);
         mean_b[3 * i + c] = (T)(sum_b[3 * i + c] * sb);
     }
-}
-
-hipError_t launch_adaptive_compact(const uint32_t* order_in, uint32_t* order_out, const double* tile_error,
-                                   int n_tiles, int n_stopped, double threshold, bool at_max, uint32_t* counts,
-                                   hipStream_t stream)
-{
-    if (n_tiles <= 0 || n_stopped < 0 || n_stopped > n_tiles) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(adaptive_compact, dim3(1), dim3(kCompactThreads), 0, stream, order_in, order_out, tile_error,
-                       n_tiles, n_stopped, threshold, (int)at_max, counts);
-    return hipGetLastError();
 }
 
 hipError_t launch_adaptive_resolve(const double* sum, const double* q, const uint32_t* tile_spp, void* mean, bool f64,

@@ -6,11 +6,13 @@
 
 namespace rtas {
 
+// v rounded up to a multiple of c (c >= 1), not clamped
+static long long round_up_ll(long long v, long long c) { return (v + c - 1) / c * c; }
+
 int round_up(int v, int chunk)
 {
     const long long c = std::max(chunk, 1);
-    const long long r = ((long long)v + c - 1) / c * c;
-    return (int)std::min<long long>(r, 0x7fffffffLL / c * c);
+    return (int)std::min<long long>(round_up_ll(v, c), 0x7fffffffLL / c * c);
 }
 
 int next_count(int64_t n, int cap, int min_r, int step_r)
@@ -18,21 +20,41 @@ int next_count(int64_t n, int cap, int min_r, int step_r)
     return (int)std::min<int64_t>(cap, n == 0 ? (int64_t)min_r : n + (int64_t)step_r);
 }
 
-const char* check_create(const rt_render_params* p, const rt_adaptive_params* ap, int auto_chunk, Schedule& s)
+// what create and the one-shot call share: a whole frame, its geometry, ap's bounds
+static const char* check_frame(const rt_render_params* p, const rt_adaptive_params* ap)
 {
     if (p->row_begin != 0 || (p->row_stride != 0 && p->row_stride != 1) || p->row_block < 0 || p->row_block > 1 ||
         p->tile_shard != 0)
-        return "rt_adaptive_state renders whole frames: the shard fields must be unset";
+        return "adaptive sampling renders whole frames: the shard fields must be unset";
     if (p->width < 2 || p->height < 2 || (long long)p->width * p->height > 0xffffffffLL || p->spp_chunk < 0 ||
-        p->max_depth < 0 || (p->spp_chunk == 0 && p->spp < 1))
+        p->max_depth < 0)
         return "bad render params";
     if ((long long)((p->width + 7) / 8) * ((p->height + 7) / 8) > 0x3fffffffLL) return "too many tiles";
     if (ap->min_spp < 2 || ap->step_spp < 1) return "bad adaptive params (min_spp >= 2, step_spp >= 1)";
+    return nullptr;
+}
+
+const char* check_create(const rt_render_params* p, const rt_adaptive_params* ap, int auto_chunk, Schedule& s)
+{
+    if (const char* msg = check_frame(p, ap)) return msg;
+    if (p->spp_chunk == 0 && p->spp < 1) return "bad render params";
     s.chunk = p->spp_chunk > 0 ? p->spp_chunk : std::max(auto_chunk, 1);
     if (ap->min_spp > 0x40000000 || ap->step_spp > 0x40000000 || s.chunk > 0x40000000)
         return "bad adaptive params (min_spp, step_spp and the chunk are at most 2^30)";
     s.min_r = round_up(ap->min_spp, s.chunk);
     s.step_r = round_up(ap->step_spp, s.chunk);
+    return nullptr;
+}
+
+const char* check_one_shot(const rt_render_params* p, const rt_adaptive_params* ap, int auto_chunk, Schedule& s)
+{
+    if (const char* msg = check_frame(p, ap)) return msg;
+    if (p->spp < 2 || (p->out_format != RT_OUT_F32 && p->out_format != RT_OUT_F64))
+        return "bad render params (adaptive sampling needs spp >= 2)";
+    if (std::isnan(ap->threshold)) return "bad adaptive params (threshold not NaN)";
+    s.chunk = p->spp_chunk > 0 ? std::min(p->spp_chunk, p->spp) : std::max(auto_chunk, 1);
+    s.min_r = (int)std::min<long long>(p->spp, round_up_ll(ap->min_spp, s.chunk));
+    s.step_r = (int)std::min<long long>(p->spp, round_up_ll(ap->step_spp, s.chunk));
     return nullptr;
 }
 

@@ -1,7 +1,7 @@
-// adaptive_state_kernel.hip — the kernels of a resumable adaptive frame (rt_adaptive_state, rt_abi.h):
-// the regroup step that chooses the tiles of the next launch, which takes adaptive_compact's place
-// for a state, and the mask of a caller's-map round. The tracing, the moments and the resolve are
-// rt_render_adaptive's (adaptive_kernel.hip). The rule is stated on the host in adaptive_schedule.cpp.
+// adaptive_state_kernel.hip — what an adaptive frame's driver (adaptive_frame.cpp: rt_render_adaptive,
+// rt_adaptive_state; rt_abi.h) launches between trace launches: the regroup step that chooses the
+// tiles of the next launch, and the mask of a caller's-map round. The moments and the resolve are
+// adaptive_kernel.hip's. The rule is stated on the host in adaptive_schedule.cpp.
 #include "adaptive_state_kernel.hpp"
 
 namespace rtk {
@@ -13,7 +13,7 @@ namespace rtk {
 //      workgroup's waves through LDS (every thread reads the 16 wave values: a broadcast);
 //   2. the size of the group (active and at n*), which fixes where the group starts;
 //   3. the stable partition: ranks from ballots and popcounts within a wave and a prefix over the
-//      waves' counts in LDS against a running base, as adaptive_compact ranks.
+//      waves' counts in LDS against a running base.
 // No atomics: the order and the record are a function of tile_spp, the errors (or the mask), the
 // threshold and the cap alone. With a mask, a tile placed in the group has its entry cleared (by
 // the thread that read it), so a caller's-map round steps every selected tile once.

@@ -1,6 +1,6 @@
-// adaptive_state_kernel.hpp — the device side of a resumable adaptive frame (rt_adaptive_state,
-// rt_abi.h; adaptive_state_kernel.hip): the regroup kernel that chooses what a launch traces, and
-// the mask of a caller's-map round. The rule is adaptive_schedule.hpp's.
+// adaptive_state_kernel.hpp — between the trace launches of an adaptive frame (rt_render_adaptive,
+// rt_adaptive_state, rt_abi.h; adaptive_state_kernel.hip): the regroup kernel that chooses what a
+// launch traces, and the mask of a caller's-map round. The rule is adaptive_schedule.hpp's.
 #pragma once
 
 #include <hip/hip_runtime.h>

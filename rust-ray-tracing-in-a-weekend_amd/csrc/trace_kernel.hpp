@@ -190,11 +190,6 @@ struct AdaptiveHalves {
 hipError_t launch_adaptive_moments(const double* samples, const AdaptiveFrame& F, int n_tiles, int n_samples,
                                    int chunk, int pos, bool close, int n_done, hipStream_t stream,
                                    const AdaptiveHalves* halves = nullptr, int first = 0);
-// order_out = [order_in's first n_stopped | the others that now stop | the others that go on];
-// a tile stops when at_max or (threshold > 0 and tile_error <= threshold); counts = {stopped, active}
-hipError_t launch_adaptive_compact(const uint32_t* order_in, uint32_t* order_out, const double* tile_error,
-                                   int n_tiles, int n_stopped, double threshold, bool at_max, uint32_t* counts,
-                                   hipStream_t stream);
 // mean (f32 / f64) = sum * (1 / tile_spp of the pixel's tile); se_map (may be null) = per-pixel se
 hipError_t launch_adaptive_resolve(const double* sum, const double* q, const uint32_t* tile_spp, void* mean, bool f64,
                                    double* se_map, int width, int height, hipStream_t stream);

@@ -2,6 +2,7 @@
 // command per line of the file given as argv[1] and prints what the module decides, for
 // tests/test_adaptive_state_host.py (built there with ASan and UBSan).
 //   create W H spp spp_chunk row_begin row_stride row_block tile_shard max_depth min_spp step_spp
+//   oneshot W H spp spp_chunk row_begin row_stride row_block tile_shard max_depth out_format min_spp step_spp threshold
 //   advance threshold spp_cap max_launches has_map ragged_cap any_zero
 //   ragged ragged_cap end chunk
 //   next n cap min_r step_r
@@ -52,6 +53,17 @@ int main(int argc, char** argv)
             rtas::Schedule s;
             const int auto_chunk = std::min(16, std::max(1, (p.spp + 15) / 16));
             const char* msg = rtas::check_create(&p, &ap, auto_chunk, s);
+            if (msg) std::printf("err %s\n", msg);
+            else std::printf("ok %d %d %d\n", s.chunk, s.min_r, s.step_r);
+        } else if (cmd == "oneshot") {
+            rt_render_params p{};
+            rt_adaptive_params ap{};
+            in >> p.width >> p.height >> p.spp >> p.spp_chunk >> p.row_begin >> p.row_stride >> p.row_block >>
+                p.tile_shard >> p.max_depth >> p.out_format >> ap.min_spp >> ap.step_spp;
+            ap.threshold = number(in);
+            rtas::Schedule s;
+            const int auto_chunk = std::min(16, std::max(1, (p.spp + 15) / 16));
+            const char* msg = rtas::check_one_shot(&p, &ap, auto_chunk, s);
             if (msg) std::printf("err %s\n", msg);
             else std::printf("ok %d %d %d\n", s.chunk, s.min_r, s.step_r);
         } else if (cmd == "advance") {

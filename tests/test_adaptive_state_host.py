@@ -3,7 +3,8 @@
 * rt_adaptive_next_group_host against the numpy rule of tests/adaptive_state_reference.py;
 * tile independence: the host rule driven one group per call over oracle-derived samples lands
   every tile where adaptive_reference.simulate's one-shot run at the last threshold does;
-* csrc/adaptive_schedule.cpp (the schedule, the ragged-cap rule, every parameter check) through
+* csrc/adaptive_schedule.cpp (the schedule, the ragged-cap rule, every parameter check of the state
+  and of rt_render_adaptive, with the one-shot call's rounding) through
   tests/adaptive_schedule_main.cpp, built with ASan and UBSan as a stand-alone program;
 * the ctypes mirrors of the new structs against gcc's offsets.
 """
@@ -174,6 +175,44 @@ def test_create_checks(schedule_main):
         "40 24 96 16 0 1 0 0 50 2000000000 16": "err",
     }
     out = schedule_main(["create " + c for c in cases])
+    for (case, want), got in zip(cases.items(), out):
+        assert got == want if want.startswith("ok") else got.startswith("err "), (case, got)
+
+
+def test_one_shot_checks_and_rounding(schedule_main):
+    """rt_render_adaptive's checks and schedule: W H spp spp_chunk row_begin row_stride row_block
+    tile_shard max_depth out_format min_spp step_spp threshold. The chunk is at most spp (as
+    rt_render's); min_spp and step_spp are rounded up to it and then capped at spp."""
+    ok = "40 24 96 16 0 1 0 0 50 1 16 16 0.02"
+    cases = {
+        ok: "ok 16 16 16",
+        "37 21 40 4 0 1 0 0 50 1 6 8 inf": "ok 4 8 8",          # test_threshold_inf_stops_at_min_spp's
+        "32 32 17 0 0 1 0 0 50 1 4 6 0": "ok 2 4 6",            # the automatic chunk for spp 17 is 2
+        "72 40 20 0 0 0 1 0 50 0 6 3 -1": "ok 2 6 4",           # row_stride 0 and row_block 1 are "unset"; f32
+        "40 24 16 64 0 1 0 0 50 1 4 4 0.02": "ok 16 16 16",     # the chunk clamped to spp
+        "40 24 40 16 0 1 0 0 50 1 16 48 0.02": "ok 16 16 40",   # the rounded step capped at spp
+        "40 24 40 16 0 1 0 0 50 1 100 16 0.02": "ok 16 40 16",  # the rounded min capped at spp
+        "40 24 17 4 0 1 0 0 50 1 18 3 0.02": "ok 4 17 4",       # rounded past spp (20), then capped
+        "40 24 2 0 0 1 0 0 0 1 2 1 0.02": "ok 1 2 1",           # the smallest call
+        "40 24 2000000000 16 0 1 0 0 50 1 2147483647 2147483647 0.02": "ok 16 2000000000 2000000000",
+        "40 24 96 16 1 1 0 0 50 1 16 16 0.02": "err",           # shard fields
+        "40 24 96 16 0 2 0 0 50 1 16 16 0.02": "err",
+        "40 24 96 16 0 1 8 0 50 1 16 16 0.02": "err",
+        "40 24 96 16 0 1 0 1 50 1 16 16 0.02": "err",
+        "40 24 96 16 0 1 0 0 50 1 1 16 0.02": "err",            # min_spp < 2
+        "40 24 96 16 0 1 0 0 50 1 16 0 0.02": "err",            # step_spp < 1
+        "1 24 96 16 0 1 0 0 50 1 16 16 0.02": "err",            # geometry
+        "40 1 96 16 0 1 0 0 50 1 16 16 0.02": "err",
+        "65536 65536 96 16 0 1 0 0 50 1 16 16 0.02": "err",     # 2^32 pixels
+        "40 24 96 -1 0 1 0 0 50 1 16 16 0.02": "err",
+        "40 24 96 16 0 1 0 0 -1 1 16 16 0.02": "err",
+        "40 24 1 0 0 1 0 0 50 1 16 16 0.02": "err",             # spp < 2
+        "40 24 1 1 0 1 0 0 50 1 16 16 0.02": "err",
+        "40 24 96 16 0 1 0 0 50 2 16 16 0.02": "err",           # out_format
+        "40 24 96 16 0 1 0 0 50 -1 16 16 0.02": "err",
+        "40 24 96 16 0 1 0 0 50 1 16 16 nan": "err",            # NaN threshold
+    }
+    out = schedule_main(["oneshot " + c for c in cases])
     for (case, want), got in zip(cases.items(), out):
         assert got == want if want.startswith("ok") else got.startswith("err "), (case, got)
 

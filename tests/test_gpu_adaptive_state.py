@@ -280,25 +280,61 @@ def test_a_callers_error_map_steps_the_selected_tiles_once(rt, renderer, device)
         st.close()
 
 
+def _stepwise(rt, st, thr, cap, min_r, step_r, most):
+    """Drives a state to (thr, cap) one launch per call. Before each launch the CPU-tested host rule
+    (rt_adaptive_next_group_host) names the group from the checkpoint's own tile_spp and tile_error
+    (the E bits the device reads, so no margin is needed); the launch must move exactly that group
+    to n_next, leave every other count, and return the host rule's active count on the new arrays.
+    Returns the launches it took (at most `most`)."""
+    launches = 0
+    while True:
+        _, arrays = st.checkpoint()
+        n = arrays["tile_spp"].reshape(-1)
+        group, n_star, n_next, _ = rt.adaptive_next_group_host(n, thr, cap, min_r, step_r,
+                                                               tile_error=arrays["tile_error"].reshape(-1))
+        assert group.size > 0 and (n[group] == n_star).all()
+        left = st.advance(thr, cap, max_launches=1)
+        assert st.stats().groups == 1
+        launches += 1
+        _, arrays = st.checkpoint()
+        exp = n.copy()
+        exp[group] = n_next
+        assert np.array_equal(arrays["tile_spp"].reshape(-1), exp), launches
+        assert left == rt.adaptive_next_group_host(exp, thr, cap, min_r, step_r,
+                                                   tile_error=arrays["tile_error"].reshape(-1))[3], launches
+        if left == 0:
+            return launches
+        assert launches < most
+
+
 def test_regroup_beyond_one_round(rt, renderer):
-    """1089 tiles: the regroup's partition loop runs twice. Both sides take E_t from the same kernel
-    on the same records, so no margin is needed. Then a checkerboard round on it."""
+    """1089 tiles: the regroup's partition loop runs twice. The state is driven one launch per call
+    and every launch held to the host rule on the state's own checkpoint (_stepwise), the final
+    frame to rt_render per count; the one-shot call, on the same driver, must land on the same
+    bits. Then a checkerboard round on it."""
     scene, W, H, chunk, mn, step, cap, thr = 4, 264, 264, 2, 2, 2, 6, 0.05
     cam, bg = _setup(rt, renderer, scene, W, H)
     p = _params(rt, bg, W, H, cap, chunk)
     ref = renderer.render_adaptive_halves(cam, p, mn, step, thr)
+    passes = renderer.adaptive_stats().passes
     assert ref[1].size == 1089 and len(set(ref[1].reshape(-1).tolist())) >= 2
     st = renderer.adaptive_state(cam, p, mn, step, halves=True)
+    one = renderer.adaptive_state(cam, p, mn, step, halves=True)
     try:
+        assert _stepwise(rt, one, thr, cap, mn, step, 3) == one.stats().groups_total == passes   # 2 -> 4 -> 6
+        f = one.resolve(rt.RT_OUT_F64)
+        _check_counts_hold_rt_render(rt, renderer, cam, bg, W, H, f, chunk)
+        _same(f, ref)
         assert st.advance(thr, cap) == 0
         _same(st.resolve(rt.RT_OUT_F64), ref)
-        assert st.stats().groups == renderer.adaptive_stats().passes
+        assert st.stats().groups == passes
         before, after, stepped = _map_round(rt, renderer, st, cam, bg, W, H, chunk, step, 8, False)
         _, arrays = st.checkpoint()
         E, se = rt.adaptive_tile_errors_host(arrays["sums"], arrays["q"], arrays["tile_spp"], W, H)
         assert ar.close(after[2], E.reshape(after[2].shape)) and ar.close(after[3], se)
     finally:
         st.close()
+        one.close()
 
 
 def test_one_tile_frame(rt, renderer):
@@ -306,14 +342,18 @@ def test_one_tile_frame(rt, renderer):
     cam, bg = _setup(rt, renderer, scene, W, H)
     p = _params(rt, bg, W, H, cap, chunk)
     st = renderer.adaptive_state(cam, p, mn, step, halves=True)
+    one = renderer.adaptive_state(cam, p, mn, step, halves=True)
     try:
         assert st.advance(thr, cap, max_launches=1) in (0, 1)
         assert st.advance(thr, cap) == 0
         f = st.resolve(rt.RT_OUT_F64)
         _same(f, renderer.render_adaptive_halves(cam, p, mn, step, thr))
         _check_counts_hold_rt_render(rt, renderer, cam, bg, W, H, f, chunk)
+        assert _stepwise(rt, one, thr, cap, mn, step, 3) == st.stats().groups_total
+        _same(one.resolve(rt.RT_OUT_F64), f)
     finally:
         st.close()
+        one.close()
 
 
 def test_context_is_untouched_and_sequences_repeat(rt, renderer):
