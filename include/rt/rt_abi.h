@@ -346,7 +346,12 @@ int rt_last_deal_order(rt_ctx* ctx, uint32_t* out, int64_t n);
  * over GPUs by 8x8 tiles: rank r of `world` renders the tiles at positions r, r + world, ... of the
  * frame's tile order (rt_render_params.tile_shard), RCCL gathers every rank's slab to rank 0 over
  * xGMI in one collective, and a reorder kernel on rank 0 writes the frame. Every draw is keyed by
- * (pixel, sample), so the frame is bit-identical to rt_render's at any world size and tile order.
+ * (pixel, sample), so in RT_PREC_F64 the frame is bit-identical to rt_render's at any world size
+ * and tile order. In RT_PREC_F32 the bits depend on the trace kernel that ran (rt_ctx_set_precision):
+ * the frame is rt_render's bit for bit whenever the shards and the whole frame take the same one
+ * (a forced schedule, and the same choice of POOL's ring or buffer), at any world size and tile
+ * order; under RT_SCHED_AUTO a shard that fits the buffer bound where the whole frame does not may
+ * take another kernel, and then agrees with it statistically only.
  *
  * A communicator binds one context (one device) to one rank. Two ways to make them:
  *   one process per GPU:     rank 0 calls rt_comm_unique_id and sends the 128 bytes to the other
@@ -1114,8 +1119,8 @@ enum {
 int rt_ctx_set_option(rt_ctx* ctx, int key, int64_t value);
 int rt_ctx_get_option(rt_ctx* ctx, int key, int64_t* value);
 
-/* Work schedule of a context (default RT_SCHED_AUTO). Images are bit-identical under all of
- * them.
+/* Work schedule of a context (default RT_SCHED_AUTO). In RT_PREC_F64 images are bit-identical
+ * under all of them; in RT_PREC_F32 each schedule's kernel rounds on its own (rt_ctx_set_precision).
  *   CHUNKS: a wave owns an 8x8 tile x one chunk of samples, each lane one pixel's chunk,
  *           written as one partial per (pixel, chunk); the wave waits for its slowest lane.
  *   POOL:   persistent waves take (tile, chunk) blocks from a device counter and a lane
@@ -1125,7 +1130,8 @@ int rt_ctx_get_option(rt_ctx* ctx, int key, int64_t* value);
  *           in one batch (RT_OPT_POOL_RING), a block belongs to one wave instead: its samples wait
  *           in that wave's ring of 4 blocks, and when the block's last sample ends the wave sums
  *           every pixel's samples in order into the chunk partial (1/chunk of the per-sample
- *           bytes, as ITEMS). Same bits either way.
+ *           bytes, as ITEMS). Same bits either way in RT_PREC_F64 (in RT_PREC_F32 the ring form is
+ *           another kernel: other last bits).
  *   ITEMS:  persistent waves as POOL, but a lane takes a whole (pixel, chunk) item, traces
  *           its samples in order and writes one partial, as CHUNKS does (1/chunk of POOL's
  *           buffer bytes); a lane whose item ended takes the next item at once.
@@ -1157,7 +1163,12 @@ int rt_ctx_set_schedule(rt_ctx* ctx, int schedule);
  *   F32: a fast mode: f32 rays, hit records, materials and textures (sphere tests keep
  *        |oc|^2 - r^2 in f64), one 32-bit draw per uniform; per-pixel sums
  *        stay f64. Statistically equal to F64 (independent-seed tests), not bitwise; never
- *        the headline metric. count_work is not available in it. */
+ *        the headline metric. count_work is not available in it. Its translation units
+ *        contract multiply-adds, and each trace kernel (CHUNKS, POOL with its buffer, POOL
+ *        with its ring, ITEMS) compiles the path code on its own, so an F32 frame depends on
+ *        the kernel that ran: rt_stats.schedule, and ring_bytes > 0 or not. For one kernel it
+ *        is bit-identical across row and tile shards, world sizes, tile orders, deal orders and
+ *        buffer batches, as every F64 frame is across all of these and across kernels too. */
 enum { RT_PREC_F64 = 0, RT_PREC_F32 = 1 };
 int rt_ctx_set_precision(rt_ctx* ctx, int precision);
 

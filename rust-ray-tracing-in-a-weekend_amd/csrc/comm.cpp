@@ -6,7 +6,9 @@
 // tiles at positions r, r + world, ... of the frame's tile order (one slab per rank, rt_render's
 // tile_shard layout), one RCCL gather moves the slabs to rank 0 over xGMI, and a reorder kernel
 // (trace_kernel.hip, assemble_tiles) writes the frame there. Every draw is keyed by (pixel,
-// sample), so the frame equals rt_render's bit for bit at any world size or tile order.
+// sample), so the frame equals rt_render's bit for bit at any world size or tile order (in the
+// f32 mode: whenever the shards and the whole frame run the same trace kernel, rt_abi.h). What a
+// rank sends and where it lands on rank 0 is stated once, in comm_layout.hpp.
 //
 // RCCL is loaded with dlopen when the first communicator is made (librccl.so.1: the process's
 // copy if one is loaded already — torch's, say — else the ROCm install's), so the library and
@@ -25,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "comm_layout.hpp"
 #include "ctx_internal.hpp"
 #include "deal_cache.hpp"
 #include "rt/rt_abi.h"
@@ -111,8 +114,7 @@ struct rt_comm {
     EventSpan<4> ev;            // render start / end, gathered, assembled; armed: a gather's events not yet read into stats
     rt_comm_stats stats{};
     bool direct = false;        // the last frame was a world-1 direct render (no slabs gathered)
-    size_t status_off = 0;      // byte offset of the status trailer in a slab (rank 0: to check the peers')
-    size_t slab_stride = 0;     // bytes per rank in recv
+    rtc::SlabLayout lay;        // the last gathered frame's slabs (rank 0: where the peers' status trailers lie in recv)
 };
 
 namespace {
@@ -125,15 +127,15 @@ bool bad_frame(const rt_render_params* p)
 }
 
 // One frame's shard on one rank: the render params of its tile shard and the slab geometry
-// (every rank's slab is padded to the largest shard's, rank 0's; + the 8-byte status trailer).
+// (comm_layout.hpp: every rank's slab is padded to the largest shard's, rank 0's; + the status trailer).
 struct Shard {
     rt_render_params q;
-    int n_max = 0, n_mine = 0;
-    long long slab_elems = 0;   // 8 x 8 n_max x 3
-    size_t esz = 8;
-    size_t slab_bytes = 0;      // slab_elems * esz + 8
+    rtc::SlabLayout lay;
 };
 
+// Every rank computes the same frame geometry from the same p, and a collective call sets the same
+// tile order on every rank's context (rt_comm_tile_order; rt_ctx_set_tile_order is the caller's to
+// keep alike), so what fails here fails on every rank alike, before any of them enqueued anything.
 int shard_of(const rt_comm* m, const rt_render_params* p, hipStream_t s, Shard& f)
 {
     if (bad_frame(p)) return fail(RT_ERR_INVALID, "bad render params");
@@ -144,12 +146,13 @@ int shard_of(const rt_comm* m, const rt_render_params* p, hipStream_t s, Shard& 
     f.q.row_stride = m->world;
     f.q.out_on_device = 1;
     f.q.stream = s;
-    f.n_max = rt_tiles_in_shard(p->width, p->height, 0, m->world);
-    f.n_mine = rt_tiles_in_shard(p->width, p->height, m->rank, m->world);
-    if (f.n_max <= 0) return fail(RT_ERR_INVALID, "frame too large for a tile shard");
-    f.esz = p->out_format == RT_OUT_F64 ? 8 : 4;
-    f.slab_elems = 192LL * f.n_max;
-    f.slab_bytes = (size_t)f.slab_elems * f.esz + 8;
+    f.lay = rtc::slab_layout(p->width, p->height, m->rank, m->world, p->out_format == RT_OUT_F64 ? 8 : 4);
+    if (f.lay.n_max <= 0) return fail(RT_ERR_INVALID, "frame too large for a tile shard");
+    // a tile order made for another frame: the shard render would refuse it, but the reorder kernel
+    // reads order[pos] for every tile position of this frame (rt_tiles_assemble refuses it alike)
+    const int64_t n_order = m->ctx->tile_order_n;
+    const int64_t n_tiles = (int64_t)((p->width + 7) / 8) * ((p->height + 7) / 8);
+    if (n_order > 0 && n_order != n_tiles) return fail(RT_ERR_INVALID, "the context's tile order is for another frame");
     return RT_OK;
 }
 
@@ -164,25 +167,25 @@ hipStream_t stream_of(const rt_comm* m, const rt_render_params* p)
 int enqueue_shard(rt_comm* m, const rt_camera* cam, const Shard& f, hipStream_t s)
 {
     HIP_TRY(hipSetDevice(m->device));
-    int rc = m->slab.reserve(s, f.slab_bytes);
+    int rc = m->slab.reserve(s, f.lay.slab_bytes);
     if (rc) return rc;
     if (m->rank == 0) {
-        rc = m->recv.reserve(s, f.slab_bytes * (size_t)m->world);
+        rc = m->recv.reserve(s, f.lay.gathered_bytes());
         if (rc) return rc;
     }
     HIP_TRY(m->ev.record(0, s));
     rc = rt_render(m->ctx, cam, &f.q, m->slab.p);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(m->ev.record(1, s));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->slab.as<char>() + f.slab_bytes - 8), rc ? -rc : 0, 2, s));
-    m->status_off = f.slab_bytes - 8;
-    m->slab_stride = f.slab_bytes;
+    static_assert(rtc::kTrailerBytes == 2 * sizeof(int32_t), "the trailer is written as two words");
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->slab.as<char>() + f.lay.status_off()), rtc::status_of(rc), 2, s));
+    m->lay = f.lay;
     return rc;
 }
 
 int enqueue_gather(const Rccl& R, rt_comm* m, const Shard& f, hipStream_t s)
 {
-    NCCL_TRY(R, R.Gather(m->slab.p, m->rank == 0 ? m->recv.p : nullptr, f.slab_bytes, ncclUint8, 0, m->nc, s));
+    NCCL_TRY(R, R.Gather(m->slab.p, m->rank == 0 ? m->recv.p : nullptr, f.lay.slab_bytes, ncclUint8, 0, m->nc, s));
     HIP_TRY(m->ev.record(2, s));
     return RT_OK;
 }
@@ -191,31 +194,39 @@ int enqueue_gather(const Rccl& R, rt_comm* m, const Shard& f, hipStream_t s)
 // copied to the caller's host memory), in the context's tile order.
 int enqueue_assemble(rt_comm* m, const rt_render_params* p, const Shard& f, hipStream_t s, void* frame)
 {
-    const size_t frame_bytes = (size_t)p->width * p->height * 3 * f.esz;
+    const size_t frame_bytes = (size_t)p->width * p->height * 3 * f.lay.esz;
     void* dst = frame;
     if (!p->out_on_device) {
         const int rc = m->stage.reserve(s, frame_bytes);
         if (rc) return rc;
         dst = m->stage.p;
     }
-    HIP_TRY(rtk::launch_assemble_tiles(m->recv.p, dst, f.esz == 8, m->world, (long long)(f.slab_bytes / f.esz),
+    HIP_TRY(rtk::launch_assemble_tiles(m->recv.p, dst, f.lay.esz == 8, m->world, f.lay.stride_elems(),
                                        p->width, p->height, m->ctx->tile_order.as<uint32_t>(), s));
     HIP_TRY(m->ev.record(3, s));
     if (!p->out_on_device) HIP_TRY(hipMemcpyAsync(frame, dst, frame_bytes, hipMemcpyDeviceToHost, s));
     return RT_OK;
 }
 
-// Rank 0 after its stream is synchronized: the peers' status trailers (RT_ERR_PEER if any failed).
+// Rank 0 once the gather has completed: the ranks' status trailers, read from the gathered slabs.
+int scan_peers(rt_comm* m, rtc::StatusScan& scan)
+{
+    std::vector<int32_t> st((size_t)m->world, 0);
+    for (int r = 0; r < m->world; ++r)
+        HIP_TRY(hipMemcpy(&st[(size_t)r], m->recv.as<char>() + m->lay.status_at(r), sizeof(int32_t), hipMemcpyDeviceToHost));
+    scan = rtc::scan_status(st.data(), m->world);
+    return RT_OK;
+}
+
+// Rank 0 after its stream is synchronized: RT_ERR_PEER if any rank's shard render failed.
 int peer_status(rt_comm* m)
 {
-    for (int r = 0; r < m->world; ++r) {
-        int32_t st = 0;
-        HIP_TRY(hipMemcpy(&st, m->recv.as<char>() + (size_t)r * m->slab_stride + m->status_off, 4,
-                          hipMemcpyDeviceToHost));
-        if (st != 0)
-            return fail(RT_ERR_PEER, "rank " + std::to_string(r) + "'s shard render failed (" + std::to_string(-st) +
-                                         "): the frame is incomplete");
-    }
+    rtc::StatusScan scan;
+    const int rc = scan_peers(m, scan);
+    if (rc) return rc;
+    if (scan.failed)
+        return fail(RT_ERR_PEER, "rank " + std::to_string(scan.first) + "'s shard render failed (" +
+                                     std::to_string(scan.first_rc) + "): the frame is incomplete");
     return RT_OK;
 }
 
@@ -223,8 +234,8 @@ void note_gather(rt_comm* m, const Shard& f)
 {
     m->ev.arm();
     m->direct = false;
-    m->stats.slab_bytes = (int64_t)f.slab_bytes;
-    m->stats.tiles = f.n_mine;
+    m->stats.slab_bytes = (int64_t)f.lay.slab_bytes;
+    m->stats.tiles = f.lay.n_mine;
 }
 
 // A world of one (RT_OPT_COMM_DIRECT, raster tile order): rt_render straight into the frame.
@@ -299,7 +310,7 @@ int cost_local(rt_comm* m, const rt_camera* cam, const rt_render_params* p, int 
     q.count_work = 1;
     q.out_format = RT_OUT_F32;
     if (!rc) rc = shard_of(m, &q, s, f);
-    if (!rc) rc = m->slab.reserve(s, f.slab_bytes);
+    if (!rc) rc = m->slab.reserve(s, f.lay.slab_bytes);
     if (!rc) rc = rt_render(m->ctx, cam, &f.q, m->slab.p);
     if (!rc) {
         const int got = rt_last_tile_costs(m->ctx, h.data(), cp.n_tiles);   // synchronizes the render
@@ -509,8 +520,9 @@ int rt_render_gather(rt_comm* m, const rt_camera* cam, const rt_render_params* p
     rc = shard_of(m, p, s, f);   // (argument errors: every rank has the same p and fails alike)
     if (rc) return rc;
     const int rc_render = enqueue_shard(m, cam, f, s);
-    if (m->slab.cap < f.slab_bytes || (m->rank == 0 && m->recv.cap < f.slab_bytes * (size_t)m->world))
-        return rc_render;   // no buffers to send from: nothing was enqueued for the peers either
+    if (m->slab.cap < f.lay.slab_bytes || (m->rank == 0 && m->recv.cap < f.lay.gathered_bytes()))
+        return rc_render;   // no buffers to send from: this rank stays out of the gather (its peers may
+                            // already have enqueued theirs, and then wait for it: DESIGN.md, known gaps)
     rc = enqueue_gather(*R, m, f, s);
     if (rc) return rc;
     note_gather(m, f);
@@ -543,14 +555,14 @@ int rt_render_gather_all(rt_comm* const* comms, int n, const rt_camera* cam, con
     for (int i = 0; i < n; ++i) {   // every render enqueued before any gather: the GPUs trace at once
         rc = enqueue_shard(comms[i], cam, f[(size_t)i], comms[i]->ctx->stream);
         if (rc && !rc_render) rc_render = rc;
-        if (comms[i]->slab.cap < f[(size_t)i].slab_bytes ||
-            (i == 0 && comms[0]->recv.cap < f[0].slab_bytes * (size_t)n))
+        if (comms[i]->slab.cap < f[(size_t)i].lay.slab_bytes ||
+            (i == 0 && comms[0]->recv.cap < f[0].lay.gathered_bytes()))
             return rc;   // no buffers: nothing to gather
     }
     NCCL_TRY(*R, R->GroupStart());
     for (int i = 0; i < n; ++i) {
         rt_comm* m = comms[i];
-        const ncclResult_t r = R->Gather(m->slab.p, i == 0 ? m->recv.p : nullptr, f[(size_t)i].slab_bytes, ncclUint8, 0,
+        const ncclResult_t r = R->Gather(m->slab.p, i == 0 ? m->recv.p : nullptr, f[(size_t)i].lay.slab_bytes, ncclUint8, 0,
                                          m->nc, m->ctx->stream);
         if (r != ncclSuccess) {
             (void)R->GroupEnd();
@@ -595,10 +607,11 @@ int rt_comm_last_stats(rt_comm* m, rt_comm_stats* out)
         rt_stats st;
         if (rt_last_stats(m->ctx, &st) == RT_OK) m->stats.kernel_ms = st.kernel_ms;
         m->stats.peer_failed = 0;
-        for (int r = 0; m->rank == 0 && !m->direct && r < m->world; ++r) {
-            int32_t v = 0;
-            HIP_TRY(hipMemcpy(&v, m->recv.as<char>() + (size_t)r * m->slab_stride + m->status_off, 4, hipMemcpyDeviceToHost));
-            m->stats.peer_failed += v != 0;
+        if (m->rank == 0 && !m->direct) {
+            rtc::StatusScan scan;
+            const int rc = scan_peers(m, scan);
+            if (rc) return rc;
+            m->stats.peer_failed = scan.failed;
         }
         m->ev.disarm();
     }
@@ -610,8 +623,8 @@ int rt_tiles_assemble(rt_ctx* ctx, const void* slabs, int64_t slab_elems, int wo
                       void* frame)
 {
     if (!ctx || !slabs || !frame || world < 1 || bad_frame(p)) return fail(RT_ERR_INVALID, "bad argument");
-    const int n_max = rt_tiles_in_shard(p->width, p->height, 0, world);
-    if (n_max <= 0 || slab_elems < 192LL * n_max) return fail(RT_ERR_INVALID, "slab_elems below the largest shard's");
+    const rtc::SlabLayout lay = rtc::slab_layout(p->width, p->height, 0, world, p->out_format == RT_OUT_F64 ? 8 : 4);
+    if (lay.n_max <= 0 || slab_elems < lay.slab_elems) return fail(RT_ERR_INVALID, "slab_elems below the largest shard's");
     const int64_t n_order = ctx->tile_order_n;
     const int64_t n_tiles = (int64_t)((p->width + 7) / 8) * ((p->height + 7) / 8);
     if (n_order > 0 && n_order != n_tiles) return fail(RT_ERR_INVALID, "the context's tile order is for another frame");
@@ -629,8 +642,8 @@ int rt_tiles_assemble_host(const void* slabs, int64_t slab_elems, int world, int
         return fail(RT_ERR_INVALID, "bad argument");
     const int tx = (width + 7) / 8;
     const int64_t n_tiles = (int64_t)tx * ((height + 7) / 8);
-    const int n_max = rt_tiles_in_shard(width, height, 0, world);
-    if (n_max <= 0 || slab_elems < 192LL * n_max) return fail(RT_ERR_INVALID, "slab_elems below the largest shard's");
+    const rtc::SlabLayout lay = rtc::slab_layout(width, height, 0, world, (size_t)elem_bytes);
+    if (lay.n_max <= 0 || slab_elems < lay.slab_elems) return fail(RT_ERR_INVALID, "slab_elems below the largest shard's");
     if (order) {
         std::vector<uint8_t> seen((size_t)n_tiles, 0);
         for (int64_t i = 0; i < n_tiles; ++i) {

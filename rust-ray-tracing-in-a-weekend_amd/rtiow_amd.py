@@ -1467,15 +1467,26 @@ def tile_order_all(comms, camera: Camera, params: RenderParams, cost_spp: int = 
                                                  ctypes.byref(params), cost_spp), "rt_comm_tile_order_all")
 
 
-def render_gather_all(comms, camera: Camera, params: RenderParams) -> np.ndarray:
-    """rt_render_gather_all over the ranks of one process: the frame in host memory."""
+def render_gather_all(comms, camera: Camera, params: RenderParams, out=None) -> np.ndarray:
+    """rt_render_gather_all over the ranks of one process: the frame in host memory (or `out`)."""
     params.out_on_device = 0
     params.stream = None
     dt = np.float64 if params.out_format == RT_OUT_F64 else np.float32
-    out = np.empty((params.height, params.width, 3), dtype=dt)
+    if out is None:
+        out = np.empty((params.height, params.width, 3), dtype=dt)
+    if out.dtype != dt or out.size != params.height * params.width * 3 or not out.flags.c_contiguous:
+        raise RTError("frame buffer of the wrong shape or type")
     _check(load_library().rt_render_gather_all(_comm_array(comms), len(comms), ctypes.byref(camera),
                                                ctypes.byref(params), out.ctypes.data), "rt_render_gather_all")
     return out
+
+
+def render_gather_all_device(comms, camera: Camera, params: RenderParams, dev_ptr: int):
+    """rt_render_gather_all, enqueued on each context's stream: rank 0's frame into a device buffer."""
+    params.out_on_device = 1
+    params.stream = None
+    _check(load_library().rt_render_gather_all(_comm_array(comms), len(comms), ctypes.byref(camera),
+                                               ctypes.byref(params), ctypes.c_void_p(dev_ptr)), "rt_render_gather_all")
 
 
 class Accumulator:
