@@ -101,11 +101,11 @@ int rt_ctx_create(int device, rt_ctx** out)
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipStreamCreateWithFlags(&c->tstream[i], hipStreamNonBlocking);
     if (e == hipSuccess) e = c->ev.create();
-    if (e == hipSuccess) e = c->ev_dn.create();
+    if (e == hipSuccess) e = c->flt_denoise.ev.create();
     if (e == hipSuccess) e = c->ev_ft.create();
-    if (e == hipSuccess) e = c->ev_at.create();
-    if (e == hipSuccess) e = c->ev_x.create();
-    if (e == hipSuccess) e = c->ev_py.create();
+    if (e == hipSuccess) e = c->flt_atrous.ev.create();
+    if (e == hipSuccess) e = c->flt_cross.ev.create();
+    if (e == hipSuccess) e = c->flt_pyramid.ev.create();
     if (e == hipSuccess) e = c->ev_pf.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_done.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_in.create(hipEventDisableTiming);

@@ -133,6 +133,15 @@ struct EventSpan {
     }
 };
 
+// What the context keeps for one post-filter (abi_filters.cpp): the last call's stats
+// (rt_*_last_stats), the timing events around its kernels, and its scratch, grown on demand.
+template <typename Stats>
+struct FilterSlot {
+    Stats stats{};
+    EventSpan<2> ev;
+    DevBuf scratch;
+};
+
 constexpr int kCounters = 32;  // count_work counters (trace_device.hpp: the trace kernels' epilogues; rt_last_counters)
 
 struct rt_ctx {
@@ -157,20 +166,13 @@ struct rt_ctx {
     bool pending_counts = false;        // the render whose span is armed counted work (rt_last_stats, rt_last_tile_costs)
     rt_stats stats{};
     rt_adaptive_stats astats{};         // the last rt_render_adaptive (rt_adaptive_last_stats)
-    rt_denoise_stats dstats{};          // the last rt_denoise (rt_denoise_last_stats)
-    EventSpan<2> ev_dn;                 //   around its kernel
+    FilterSlot<rt_denoise_stats> flt_denoise;   // rt_denoise, rt_denoise_guided: no scratch
     rt_features_stats fstats{};         // the last rt_render_features (rt_features_last_stats)
     EventSpan<3> ev_ft;                 //   before its trace launches, after them, after its reductions
-    rt_atrous_stats wstats{};           // the last rt_denoise_atrous (rt_atrous_last_stats)
-    EventSpan<2> ev_at;                 //   around its level kernels
-    DevBuf atrous_buf;                  //   its state scratch between levels (rtk::AtrousRec)
-    rt_cross_stats xstats{};            // the last rt_denoise_cross (rt_cross_last_stats)
-    EventSpan<2> ev_x;                  //   around its kernels
-    DevBuf cross_buf;                   //   e(p) between its two kernels (f64 per pixel; only with stderr_out)
-    rt_pyramid_stats pstats{};          // the last rt_denoise_pyramid (rt_pyramid_last_stats)
-    EventSpan<2> ev_py;                 //   around its kernels
-    DevBuf pyramid_buf;                 //   its levels' f64 frames (rtk::PyramidLayout; none at one level)
-    EventSpan<2> ev_pf;                 //   fork and join of its coarse levels' filters on tstream[0] (ordering events)
+    FilterSlot<rt_atrous_stats> flt_atrous;     // rt_denoise_atrous: its state between levels (rtk::AtrousRec)
+    FilterSlot<rt_cross_stats> flt_cross;       // rt_denoise_cross: e(p) between its two kernels (f64 per pixel; only with stderr_out)
+    FilterSlot<rt_pyramid_stats> flt_pyramid;   // rt_denoise_pyramid: its levels' f64 frames (rtk::PyramidLayout; none at one level)
+    EventSpan<2> ev_pf;                 //   fork and join of the pyramid's coarse levels' filters on tstream[0] (ordering events)
     // what a render's launch plan is made from (launch_plan.hpp): the uploaded scene, the device, the switches
     rtp::SceneFacts scene;
     rtp::DeviceFacts dev;

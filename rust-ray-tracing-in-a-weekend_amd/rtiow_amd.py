@@ -479,6 +479,13 @@ def _check(rc: int, what: str) -> None:
         raise RTError(f"{what} failed: {ERRORS.get(rc, rc)} {msg}")
 
 
+def _stats(owner, fn_name: str, Struct):
+    """Struct as the last-stats export fn_name fills it for owner's handle."""
+    s = Struct()
+    _check(getattr(owner.lib, fn_name)(owner.h, ctypes.byref(s)), fn_name)
+    return s
+
+
 def _d3(v: Sequence[float]):
     return (ctypes.c_double * 3)(*[float(x) for x in v])
 
@@ -819,6 +826,13 @@ def denoise_host(mean, se, radius: int = 10, patch: int = 3, k: float = 0.45) ->
     return out
 
 
+def _guides(albedo_ptr, normal_ptr, depth_ptr, sigmas):
+    """rt_denoise_guides from the three frames' addresses (0 or None leaves one out) and
+    sigmas = (albedo, normal, depth)."""
+    sa, sn, sz = (float(v) for v in sigmas)
+    return DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+
+
 def _guide_args(shape, albedo, normal, depth, sigmas):
     """(rt_denoise_guides, the arrays it points into) of a host-pointer guided call: albedo and normal
     height x width x 3, depth height x width, f64; None leaves a guide out."""
@@ -834,9 +848,8 @@ def _guide_args(shape, albedo, normal, depth, sigmas):
         keep.append(a)
         return a.ctypes.data
 
-    sa, sn, sz = (float(v) for v in sigmas)
-    g = DenoiseGuides(arr(albedo, (H, W, 3), "albedo"), arr(normal, (H, W, 3), "normal"), arr(depth, (H, W), "depth"),
-                      sa, sn, sz)
+    g = _guides(arr(albedo, (H, W, 3), "albedo"), arr(normal, (H, W, 3), "normal"), arr(depth, (H, W), "depth"),
+                sigmas)
     return g, keep
 
 
@@ -1135,8 +1148,7 @@ class Renderer:
         """Enqueues rt_denoise_guided over device buffers on `stream`: as denoise_device, with the
         guide frames (f64; 0 leaves one out) render_features_device wrote."""
         p = DenoiseParams(int(width), int(height), int(out_format), 1, int(radius), int(patch), float(k), stream)
-        sa, sn, sz = (float(v) for v in sigmas)
-        g = DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+        g = _guides(albedo_ptr, normal_ptr, depth_ptr, sigmas)
         _check(self.lib.rt_denoise_guided(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr),
                                           ctypes.c_void_p(stderr_ptr), ctypes.byref(g), ctypes.c_void_p(out_ptr)),
                "rt_denoise_guided")
@@ -1166,16 +1178,13 @@ class Renderer:
         stderr_out_ptr (height x width f64; 0 leaves it out) receives the standard error left."""
         p = AtrousParams(int(width), int(height), int(out_format), 1, int(levels), int(demodulate), float(sigma_l),
                          stream)
-        sa, sn, sz = (float(v) for v in sigmas)
-        g = DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+        g = _guides(albedo_ptr, normal_ptr, depth_ptr, sigmas)
         _check(self.lib.rt_denoise_atrous(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr),
                                           ctypes.c_void_p(stderr_ptr), ctypes.byref(g), ctypes.c_void_p(out_ptr),
                                           ctypes.c_void_p(stderr_out_ptr or None)), "rt_denoise_atrous")
 
     def atrous_stats(self) -> AtrousStats:
-        s = AtrousStats()
-        _check(self.lib.rt_atrous_last_stats(self.h, ctypes.byref(s)), "rt_atrous_last_stats")
-        return s
+        return _stats(self, "rt_atrous_last_stats", AtrousStats)
 
     def denoise_pyramid(self, mean, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
                         radius: int = PYRAMID_WINDOW[0], patch: int = PYRAMID_WINDOW[1], k: float = PYRAMID_WINDOW[2],
@@ -1198,16 +1207,13 @@ class Renderer:
         """Enqueues rt_denoise_pyramid over device buffers on `stream`: as denoise_guided_device."""
         p = PyramidParams(int(width), int(height), int(out_format), 1, int(radius), int(patch), float(k), int(levels),
                           0, stream)
-        sa, sn, sz = (float(v) for v in sigmas)
-        g = DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+        g = _guides(albedo_ptr, normal_ptr, depth_ptr, sigmas)
         _check(self.lib.rt_denoise_pyramid(self.h, ctypes.byref(p), ctypes.c_void_p(mean_ptr),
                                            ctypes.c_void_p(stderr_ptr), ctypes.byref(g), ctypes.c_void_p(out_ptr)),
                "rt_denoise_pyramid")
 
     def pyramid_stats(self) -> PyramidStats:
-        s = PyramidStats()
-        _check(self.lib.rt_pyramid_last_stats(self.h, ctypes.byref(s)), "rt_pyramid_last_stats")
-        return s
+        return _stats(self, "rt_pyramid_last_stats", PyramidStats)
 
     def denoise_cross(self, mean_a, mean_b, se, albedo=None, normal=None, depth=None, sigmas=GUIDE_SIGMAS,
                       radius: int = 10, patch: int = 3, k: float = 0.45,
@@ -1234,17 +1240,14 @@ class Renderer:
         map."""
         p = CrossParams(int(width), int(height), int(out_format), 1, int(radius), int(patch), float(k),
                         float(variance_scale), stream)
-        sa, sn, sz = (float(v) for v in sigmas)
-        g = DenoiseGuides(albedo_ptr or None, normal_ptr or None, depth_ptr or None, sa, sn, sz)
+        g = _guides(albedo_ptr, normal_ptr, depth_ptr, sigmas)
         _check(self.lib.rt_denoise_cross(self.h, ctypes.byref(p), ctypes.c_void_p(mean_a_ptr),
                                          ctypes.c_void_p(mean_b_ptr), ctypes.c_void_p(stderr_ptr), ctypes.byref(g),
                                          ctypes.c_void_p(out_ptr), ctypes.c_void_p(stderr_out_ptr or None)),
                "rt_denoise_cross")
 
     def cross_stats(self) -> CrossStats:
-        s = CrossStats()
-        _check(self.lib.rt_cross_last_stats(self.h, ctypes.byref(s)), "rt_cross_last_stats")
-        return s
+        return _stats(self, "rt_cross_last_stats", CrossStats)
 
     def render_features(self, camera: Camera, params: RenderParams, albedo: bool = True, normal: bool = True,
                         depth: bool = True):
@@ -1271,19 +1274,13 @@ class Renderer:
                "rt_render_features")
 
     def features_stats(self) -> FeaturesStats:
-        s = FeaturesStats()
-        _check(self.lib.rt_features_last_stats(self.h, ctypes.byref(s)), "rt_features_last_stats")
-        return s
+        return _stats(self, "rt_features_last_stats", FeaturesStats)
 
     def denoise_stats(self) -> DenoiseStats:
-        s = DenoiseStats()
-        _check(self.lib.rt_denoise_last_stats(self.h, ctypes.byref(s)), "rt_denoise_last_stats")
-        return s
+        return _stats(self, "rt_denoise_last_stats", DenoiseStats)
 
     def adaptive_stats(self) -> AdaptiveStats:
-        s = AdaptiveStats()
-        _check(self.lib.rt_adaptive_last_stats(self.h, ctypes.byref(s)), "rt_adaptive_last_stats")
-        return s
+        return _stats(self, "rt_adaptive_last_stats", AdaptiveStats)
 
     def adaptive_state(self, camera: Camera, params: RenderParams, min_spp: int, step_spp: int,
                        halves: bool = False) -> "AdaptiveState":
@@ -1353,9 +1350,7 @@ class Renderer:
         _check(self.lib.rt_ctx_set_tile_order(self.h, o.ctypes.data, len(o)), "rt_ctx_set_tile_order")
 
     def stats(self) -> Stats:
-        s = Stats()
-        _check(self.lib.rt_last_stats(self.h, ctypes.byref(s)), "rt_last_stats")
-        return s
+        return _stats(self, "rt_last_stats", Stats)
 
     def assemble_device(self, slabs_ptr: int, slab_elems: int, world: int, params: RenderParams, frame_ptr: int,
                         stream: Optional[int] = None):
@@ -1451,9 +1446,7 @@ class Comm:
                                          ctypes.c_void_p(dev_ptr) if dev_ptr else None), "rt_render_gather")
 
     def stats(self) -> CommStats:
-        s = CommStats()
-        _check(self.lib.rt_comm_last_stats(self.h, ctypes.byref(s)), "rt_comm_last_stats")
-        return s
+        return _stats(self, "rt_comm_last_stats", CommStats)
 
 
 def _comm_array(comms):
@@ -1650,9 +1643,7 @@ class AdaptiveState:
         _check(self.lib.rt_adaptive_state_set(self.h, ctypes.byref(header), ctypes.byref(data)), "rt_adaptive_state_set")
 
     def stats(self) -> AdaptiveStateStats:
-        s = AdaptiveStateStats()
-        _check(self.lib.rt_adaptive_state_last_stats(self.h, ctypes.byref(s)), "rt_adaptive_state_last_stats")
-        return s
+        return _stats(self, "rt_adaptive_state_last_stats", AdaptiveStateStats)
 
 
 def render_scene(scene_id: int, width: int, height: int, spp: int, max_depth: int = 50, scene_seed: int = 1,

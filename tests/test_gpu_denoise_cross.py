@@ -177,6 +177,38 @@ def test_device_pointer_chain_is_the_host_pointer_chain(rt, renderer, name, fmt)
     assert so_d.cpu().numpy().tobytes() == want_se.tobytes()
 
 
+def test_scratch_grows_with_work_in_flight(rt, renderer):
+    """On a context of its own (no scratch yet): frames of size A, the larger B, then A again, in f64
+    with stderr_out, enqueued back to back on one torch stream with one synchronisation at the end;
+    each out and stderr_out equals its host-pointer result bit for bit. The second call grows the e
+    scratch while the first may still run."""
+    import torch
+    frames = [_frame(rt, renderer, n) for n in ("random_ragged", "cornell", "random_ragged")]
+    own = rt.Renderer(0)
+    try:
+        stream = torch.cuda.Stream(torch.device("cuda", 0))
+        dev = []
+        for _, a, b, se, _ in frames:
+            t = [torch.from_numpy(np.array(x)).to("cuda:0") for x in (a, b, se)]
+            t += [torch.full(a.shape, 7.0, dtype=torch.float64, device="cuda:0"),
+                  torch.full(se.shape, 7.0, dtype=torch.float64, device="cuda:0")]
+            dev.append(t)
+        torch.cuda.synchronize()
+        for a_d, b_d, se_d, out_d, so_d in dev:
+            H, W = se_d.shape
+            own.denoise_cross_device(a_d.data_ptr(), b_d.data_ptr(), se_d.data_ptr(), out_d.data_ptr(), W, H,
+                                     out_format=rt.RT_OUT_F64, radius=10, patch=3, k=0.45, variance_scale=cr.SCALE,
+                                     stderr_out_ptr=so_d.data_ptr(), stream=stream.cuda_stream)
+        torch.cuda.synchronize()
+        assert own.cross_stats().scratch_bytes == 8 * 37 * 21
+        for i, ((_, a, b, se, _), t) in enumerate(zip(frames, dev)):
+            want, want_se = own.denoise_cross(a, b, se, radius=10, patch=3, k=0.45, variance_scale=cr.SCALE)
+            assert t[3].cpu().numpy().tobytes() == want.tobytes(), i
+            assert t[4].cpu().numpy().tobytes() == want_se.tobytes(), i
+    finally:
+        own.close()
+
+
 def test_fresh_context_without_a_scene(rt, renderer):
     _, a, b, se, _ = _frame(rt, renderer, "random_ragged")
     want, want_se = renderer.denoise_cross(a, b, se, radius=5, patch=2, k=1.0)
