@@ -731,21 +731,21 @@ int rt_last_stats(rt_ctx* c, rt_stats* out)
         unsigned long long (&h)[kCounters] = c->raw_counters;   // (zeros when the render counted no work)
         std::memset(h, 0, sizeof h);
         if (c->pending_counts) HIP_TRY(hipMemcpy(h, c->counters.p, sizeof h, hipMemcpyDeviceToHost));
-        c->stats.casts = h[0];
-        c->stats.node_visits = h[1];
-        c->stats.prim_tests = h[2];
-        c->stats.cycles_camera = h[3];
-        c->stats.cycles_trace = h[4];
-        c->stats.cycles_shade = h[5];
-        c->stats.wave_steps = h[6];
-        c->stats.wave_node_steps = h[7];
-        c->stats.cycles_nodes = h[8];
-        c->stats.cycles_leaves = h[9];
-        c->stats.wave_leaf_steps = h[10];
-        c->stats.camera_lanes = h[11];
-        c->stats.camera_steps = h[12];
-        c->stats.shade_lanes = h[13];
-        c->stats.shade_steps = h[14];
+        c->stats.casts = h[rtk::kCtrCasts];
+        c->stats.node_visits = h[rtk::kCtrNodeVisits];
+        c->stats.prim_tests = h[rtk::kCtrPrimTests];
+        c->stats.cycles_camera = h[rtk::kCtrCyclesCamera];
+        c->stats.cycles_trace = h[rtk::kCtrCyclesTrace];
+        c->stats.cycles_shade = h[rtk::kCtrCyclesShade];
+        c->stats.wave_steps = h[rtk::kCtrWaveSteps];
+        c->stats.wave_node_steps = h[rtk::kCtrWaveNodeSteps];
+        c->stats.cycles_nodes = h[rtk::kCtrCyclesNodes];
+        c->stats.cycles_leaves = h[rtk::kCtrCyclesLeaves];
+        c->stats.wave_leaf_steps = h[rtk::kCtrWaveLeafSteps];
+        c->stats.camera_lanes = h[rtk::kCtrCameraLanes];
+        c->stats.camera_steps = h[rtk::kCtrCameraSteps];
+        c->stats.shade_lanes = h[rtk::kCtrShadeLanes];
+        c->stats.shade_steps = h[rtk::kCtrShadeSteps];
     }
     *out = c->stats;
     return RT_OK;

@@ -142,7 +142,7 @@ struct FilterSlot {
     DevBuf scratch;
 };
 
-constexpr int kCounters = 32;  // count_work counters (trace_device.hpp: the trace kernels' epilogues; rt_last_counters)
+using rtk::kCounters;   // count_work counters (trace_kernel.hpp, CounterSlot; rt_last_counters)
 
 struct rt_ctx {
     int device = 0;

@@ -1,7 +1,9 @@
 // features_device.hpp — rt_render_features' kernel (include/rt/rt_abi.h): the first hit's albedo,
-// normal and depth per (pixel, sample), over the megakernel's device functions (trace_device.hpp:
-// camera_ray, trace_world, tex_value, stage_lds). Only the features_v_*.hip translation units
-// include it; the trace variants (trace_v_*.hip, trace_f32_*.hip) hold none of it.
+// normal and depth per (pixel, sample), over the megakernel's device functions (trace_shade.hpp and
+// the layers below it: camera_ray, trace_world, tex_value, stage_lds; trace_grid.hpp: lane_work).
+// It includes neither schedule (trace_chunks.hpp, trace_pool.hpp). Only the features_v_*.hip
+// translation units and features_kernel.hip include it; the trace variants (trace_v_*.hip,
+// trace_f32_*.hip) hold none of it.
 //
 // trace_chunks' layout without its bounce loop: one wave owns one 8x8 tile x one chunk of samples,
 // one lane one pixel. Per sample the lane seeds the path stream and shoots the primary ray exactly
@@ -18,7 +20,9 @@
 // its trace_chunks twin's VGPR count, with about the same few dwords of scratch where that one
 // has them (the compiler's figures: DESIGN.md §5.10).
 #pragma once
-#include "trace_launch.hpp"
+#include "trace_shade.hpp"
+#include "trace_grid.hpp"
+#include "trace_launch_common.hpp"
 #include "features_kernel.hpp"
 
 namespace rtk {

@@ -1,7 +1,7 @@
 // launch_shapes.hpp — the shape of a trace launch, stated once: which Cfg<F, S32, LDS, NALL, COUNT,
 // F32> instantiation runs (KernelShape), its workgroup size, its launch bound and its dynamic-LDS
-// layout (lds_layout). The kernels read the shape of their configuration (trace_device.hpp), the
-// launchers resolve it from a scene and its options (trace_launch.hpp), the host's plan carries it
+// layout (lds_layout). The kernels read the shape of their configuration (trace_types.hpp, Cfg), the
+// launchers resolve it from a scene and its options (trace_launch_common.hpp), the host's plan carries it
 // (launch_plan.cpp). Also the in-kernel reduction's ring and the per-sample buffer's record
 // count. No HIP: shared by the kernels (through trace_kernel.hpp), the plan and CPU tests.
 #pragma once
@@ -106,7 +106,7 @@ namespace rtk {
 #define RT_MIN_WAVES_F32_FINAL RT_MIN_WAVES_FINAL
 #endif
 
-// Bytes of the records a workgroup stages in LDS (trace_device.hpp asserts them against the types):
+// Bytes of the records a workgroup stages in LDS (trace_walk.hpp asserts them against the types):
 // rt_bvh_node, the whole-TLAS f32-slab node LdsNode, rt_material, rt_texture. (A staged sample
 // start's slot: kSeedSlotBytes below.)
 constexpr size_t kBvhNodeBytes = 64, kLdsNodeBytes = 80, kMaterialBytes = 64, kTextureBytes = 96;

@@ -392,7 +392,7 @@ int lower(const rt_scene_soa& s, bool hoist, Lowered& L, std::string& err)
     }
 
     if (hoist) hoist_root_leaf(s, L);
-    // Stack16 (trace_device.hpp): node records (kLdsNodeBytes each) at LDS addresses < 32 KB, BLAS node
+    // Stack16 (trace_types.hpp): node records (kLdsNodeBytes each) at LDS addresses < 32 KB, BLAS node
     // indices < 32768, and leaf codes ((first slot << 5) | count, stored complemented; BLAS slots
     // relative, above) strictly above the -32768 = ~32767 sentinel: every code < 32767 (a leaf
     // at first slot 1023 holding 31 primitives would complement to the sentinel itself)

@@ -1,6 +1,7 @@
 // trace_kernel.hip — host-side dispatch of the megakernel (the variants live in
 // trace_v*.hip over trace_device.hpp, their launcher in trace_launch.hpp), the per-pixel reductions
-// of the schedules, and the device numerics probe. See trace_device.hpp for the execution model.
+// of the schedules, and the device numerics probe. See trace_device.hpp for the execution model
+// and the map of its layers.
 #include "trace_launch.hpp"
 
 namespace rtk {
@@ -22,44 +23,13 @@ __device__ __forceinline__ bool tile_slot(SampleTiles g, int n_samples, long lon
 
 // Per pixel: chunk sums of consecutive samples (chunk order, each from 0.0), added in
 // chunk order to 0.0 and scaled into out: the same additions, in the same order, as the
-// chunk schedule's lane sums + reduce_chunks.
-template <typename T, typename Rec = double>
-__global__ void __launch_bounds__(256) reduce_samples(const Rec* __restrict__ samples, T* __restrict__ out,
-                                                      SampleTiles g, long long n_slots, int n_samples, int chunk,
-                                                      double scale)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    long long px;
-    size_t rec;
-    if (i >= n_slots || !tile_slot(g, n_samples, i, px, rec)) return;
-    double r = 0.0, g_ = 0.0, b = 0.0;
-    for (int c0 = 0; c0 < n_samples; c0 += chunk) {
-        const int c1 = min(n_samples, c0 + chunk);
-        double cr = 0.0, cg = 0.0, cb = 0.0;
-        for (int j = c0; j < c1; ++j) {
-            const Rec* p = samples + (rec + (size_t)j * 64) * 3;
-            cr = cr + (double)p[0];
-            cg = cg + (double)p[1];
-            cb = cb + (double)p[2];
-        }
-        r = r + cr;
-        g_ = g_ + cg;
-        b = b + cb;
-    }
-    out[3 * px + 0] = (T)(r * scale);
-    out[3 * px + 1] = (T)(g_ * scale);
-    out[3 * px + 2] = (T)(b * scale);
-}
-
-// reduce_samples with one block per 8x8 tile: wave w of kReduceWaves sums chunks w, w + W, ... of
-// the tile's 64 pixels (each chunk from 0.0, its samples in order, four samples' loads in flight),
-// parks the chunk sums in LDS, and wave 0 adds a round's W chunk sums in chunk order to the running
-// total: reduce_samples' additions in reduce_samples' order (bit-identical), with W waves' loads
-// in flight per tile instead of one lane's walk over every sample, and no tail of long per-pixel
+// chunk schedule's lane sums + reduce_chunks. One block per 8x8 tile: wave w of kReduceWaves sums
+// chunks w, w + W, ... of the tile's 64 pixels (each chunk from 0.0, its samples in order, four
+// samples' loads in flight), parks the chunk sums in LDS, and wave 0 adds a round's W chunk sums
+// in chunk order to the running total. That is one lane's walk over a pixel's samples, chunk by
+// chunk (the first, one-thread-per-pixel form of this reduction), addition for addition and
+// bit-identical to it, with W waves' loads in flight per tile and no tail of long per-pixel
 // loops at the end of the launch.
-#ifndef RT_REDUCE_TILED
-#define RT_REDUCE_TILED 1
-#endif
 constexpr int kReduceWaves = 8;
 template <typename T, typename Rec = double>
 __global__ void __launch_bounds__(64 * kReduceWaves) reduce_samples_tiled(const Rec* __restrict__ samples,
@@ -334,40 +304,22 @@ hipError_t launch_trace(const SceneDev& S, const KParams& Ph, const KParams* P, 
 hipError_t launch_reduce_samples(const double* samples, void* out, bool f64, SampleTiles g, int n_samples,
                                  int chunk, double scale, hipStream_t stream)
 {
-    const long long n_slots = (long long)tiled_pixels(g.width, g.n_rows);
+    const long long tiles = (long long)tiled_pixels(g.width, g.n_rows) / 64;   // one block per tile
     const float* rec32 = reinterpret_cast<const float*>(samples);
-    if (RT_REDUCE_TILED) {   // one block per tile
-        const long long tiles = n_slots / 64;
-        if (tiles <= 0 || chunk < 1) return tiles <= 0 ? hipSuccess : hipErrorInvalidValue;
-        const dim3 grid((unsigned)tiles), block(64 * kReduceWaves);
-        if (g.f32_records && f64)
-            hipLaunchKernelGGL((reduce_samples_tiled<double, float>), grid, block, 0, stream, rec32, (double*)out, g,
-                               n_samples, chunk, scale);
-        else if (g.f32_records)
-            hipLaunchKernelGGL((reduce_samples_tiled<float, float>), grid, block, 0, stream, rec32, (float*)out, g,
-                               n_samples, chunk, scale);
-        else if (f64)
-            hipLaunchKernelGGL(reduce_samples_tiled<double>, grid, block, 0, stream, samples, (double*)out, g, n_samples,
-                               chunk, scale);
-        else
-            hipLaunchKernelGGL(reduce_samples_tiled<float>, grid, block, 0, stream, samples, (float*)out, g, n_samples,
-                               chunk, scale);
-        return hipGetLastError();
-    }
-    const long long blocks = (n_slots + 255) / 256;
-    if (blocks <= 0) return hipSuccess;
+    if (tiles <= 0 || chunk < 1) return tiles <= 0 ? hipSuccess : hipErrorInvalidValue;
+    const dim3 grid((unsigned)tiles), block(64 * kReduceWaves);
     if (g.f32_records && f64)
-        hipLaunchKernelGGL((reduce_samples<double, float>), dim3((unsigned)blocks), dim3(256), 0, stream, rec32,
-                           (double*)out, g, n_slots, n_samples, chunk, scale);
+        hipLaunchKernelGGL((reduce_samples_tiled<double, float>), grid, block, 0, stream, rec32, (double*)out, g,
+                           n_samples, chunk, scale);
     else if (g.f32_records)
-        hipLaunchKernelGGL((reduce_samples<float, float>), dim3((unsigned)blocks), dim3(256), 0, stream, rec32,
-                           (float*)out, g, n_slots, n_samples, chunk, scale);
+        hipLaunchKernelGGL((reduce_samples_tiled<float, float>), grid, block, 0, stream, rec32, (float*)out, g,
+                           n_samples, chunk, scale);
     else if (f64)
-        hipLaunchKernelGGL(reduce_samples<double>, dim3((unsigned)blocks), dim3(256), 0, stream, samples, (double*)out,
-                           g, n_slots, n_samples, chunk, scale);
+        hipLaunchKernelGGL(reduce_samples_tiled<double>, grid, block, 0, stream, samples, (double*)out, g, n_samples,
+                           chunk, scale);
     else
-        hipLaunchKernelGGL(reduce_samples<float>, dim3((unsigned)blocks), dim3(256), 0, stream, samples, (float*)out,
-                           g, n_slots, n_samples, chunk, scale);
+        hipLaunchKernelGGL(reduce_samples_tiled<float>, grid, block, 0, stream, samples, (float*)out, g, n_samples,
+                           chunk, scale);
     return hipGetLastError();
 }
 

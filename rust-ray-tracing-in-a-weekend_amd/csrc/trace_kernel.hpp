@@ -104,7 +104,7 @@ struct KParams {
 // because the kernel holds both in registers anyway.
 constexpr int32_t kDealOrdered = 2, kDealMeasure = 3;
 constexpr unsigned kDealTable = 16;   // words from the counter to the table (the counter keeps its cache line)
-// the kernel variants that carry it (trace_device.hpp, DealCfg): the spheres variants. The others
+// the kernel variants that carry it (trace_pool.hpp, DealCfg): the spheres variants. The others
 // hold their block state at the SGPR limit (RingSgpr) and keep raster order.
 constexpr bool deal_variant(uint32_t variant) { return variant == FEAT_SET_SPHERES; }
 
@@ -117,6 +117,49 @@ struct LaunchOpts {
     int f32;            // the f32 fast mode (RT_PREC_F32)
     int* waves_per_simd = nullptr;  // out (optional): resident waves per SIMD of the launched trace kernel
 };
+
+// The count_work counters (LaunchOpts.count; u64 each), by slot: what the trace kernels' epilogues
+// add to (trace_chunks the first 15 and the two ray-generation parts, trace_pool all of them) and
+// rt_last_stats / rt_last_counters read back. include/rt/rt_abi.h documents the same list under
+// rt_last_counters, by number: that is the public statement, and these are its names.
+enum CounterSlot : int {
+    kCtrCasts = 0,            // rays cast
+    kCtrNodeVisits = 1,       // BVH nodes visited, per lane
+    kCtrPrimTests = 2,        // primitive tests, per lane
+    kCtrCyclesCamera = 3,     // wave-cycles: ray generation, all of it
+    kCtrCyclesTrace = 4,      //   trace (pool kernels: from the ray set-up to the hit record)
+    kCtrCyclesShade = 5,      //   shading
+    kCtrWaveSteps = 6,        // bounce-loop iterations per wave, summed
+    kCtrWaveNodeSteps = 7,    // node-visit iterations per wave, summed
+    kCtrCyclesNodes = 8,      // wave-cycles: node loops of the top-level walk
+    kCtrCyclesLeaves = 9,     //   its leaf tests
+    kCtrWaveLeafSteps = 10,   // leaf-loop iterations per wave, summed
+    kCtrCameraLanes = 11,     // lanes starting a sample,
+    kCtrCameraSteps = 12,     //   and the wave iterations in which any did
+    kCtrShadeLanes = 13,      // lanes shading a hit,
+    kCtrShadeSteps = 14,      //   and the wave iterations in which any did
+    // pool kernels only, wave-cycles per finer phase
+    kCtrCyclesSetup = 15,     // ray set-up
+    kCtrCyclesPre = 16,       // the walk's prologue (pre-leaf test)
+    kCtrCyclesRecord = 17,    // the hit record
+    kCtrCyclesMedia = 18,     // media, inside the leaf tests
+    kCtrCyclesInstances = 19, // instances, inside the leaf tests
+    kCtrCyclesRefill = 20,    // refill
+    kCtrCyclesKernel = 21,    // the waves' lifetimes, summed
+    kCtrCyclesDeferred = 22,  // deferred instance walks, after the top-level walk
+    kCtrCyclesSeed = 23,      // ray generation's seeding + jitter
+    kCtrCyclesTries = 24,     // ray generation's rejection loop
+    kCtrLongestWave = 25,     // the longest wave lifetime
+    kCtrWaves = 26,           // waves
+    // pool kernels only, bounce-loop lane slots that cast nothing (with casts: 64 x wave_steps)
+    kCtrIdleTail = 27,        // idle, no unit left to take (the launch's tail)
+    kCtrIdleRing = 28,        // idle, every ring slot holding an unfinished block
+    kCtrNoScatter = 29,       // the path ended in its scatter
+    kCtrDepthCap = 30,        // the depth cap
+    kCtrTryWait = 31,         // a rejection loop carried to the next iteration
+};
+constexpr int kCounters = kCtrTryWait + 1;
+static_assert(kCounters == 32, "rt_last_counters documents 32 slots");
 
 // Per-sample pool output: [8x8 tile][sample of the batch][64 pixels of the tile, row-major]
 // radiance records (f64 x 3). A wave's work block is one tile x consecutive samples and its
