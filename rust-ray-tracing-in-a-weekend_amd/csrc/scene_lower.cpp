@@ -8,6 +8,7 @@
 #include <unordered_map>
 
 #include "rt/rt_abi.h"
+#include "bvh_build.hpp"       // stack_need
 #include "launch_shapes.hpp"   // kLdsNodeBytes
 #include "scene_features.hpp"
 
@@ -49,41 +50,6 @@ void walk(const rt_scene_soa& s, int ref, std::vector<uint8_t>* seen, NodeFn nod
         todo.push_back(s.nodes[r].child[0]);
         todo.push_back(s.nodes[r].child[1]);
     }
-}
-
-// Stack entries a walk from `ref` needs, the way the kernel's visit uses its stack (push
-// the farther child when both are hit; with two identical child boxes child 0 is always
-// taken first, so only it stacks above the pushed child 1) — the rule flatten.cpp's
-// stack_need builds with, recomputed here from the tables alone. Iterative post-order
-// with three colours, so a cycle in a foreign node graph is found instead of walked
-// forever (the persistent kernel would spin on it). Returns -1 on a cycle.
-int walk_need(const rt_scene_soa& s, int ref, std::vector<int>& need, std::vector<uint8_t>& colour)
-{
-    if (ref < 0) return 0;
-    std::vector<int> todo{ref};
-    while (!todo.empty()) {
-        const int i = todo.back();
-        if (colour[i] == 2) {
-            todo.pop_back();
-            continue;
-        }
-        const rt_bvh_node& nd = s.nodes[i];
-        if (colour[i] == 0) {
-            colour[i] = 1;  // on the current path
-            for (int ch : nd.child) {
-                if (ch < 0 || colour[ch] == 2) continue;
-                if (colour[ch] == 1) return -1;  // back edge
-                todo.push_back(ch);
-            }
-            continue;
-        }
-        todo.pop_back();  // both children done
-        auto nc = [&](int ch) { return ch < 0 ? 0 : need[ch]; };
-        const bool same = std::memcmp(nd.lo0, nd.lo1, 12) == 0 && std::memcmp(nd.hi0, nd.hi1, 12) == 0;
-        need[i] = same ? std::max(1 + nc(nd.child[0]), nc(nd.child[1])) : 1 + std::max(nc(nd.child[0]), nc(nd.child[1]));
-        colour[i] = 2;
-    }
-    return need[ref];
 }
 
 // pre_leaf: a root child that is a leaf of <= 2 primitives whose box holds at least 8x the
@@ -200,24 +166,25 @@ int validate(const rt_scene_soa& s, int& tlas_depth, int& blas_depth, int& n_tla
         if (in.child_kind == RT_CHILD_PRIM && s.prims[in.child].kind == RT_PRIM_MEDIUM)
             return fail(RT_ERR_UNSUPPORTED, "a medium's boundary holds a medium");
     }
-    // stack needs (the kernel: TLAS walk in entries [0, tlas), a nested BLAS walk above it)
-    std::vector<int> need((size_t)s.n_nodes, 0);
-    std::vector<uint8_t> colour((size_t)s.n_nodes, 0);
-    const int t = walk_need(s, s.tlas_root, need, colour);
+    // stack needs (the kernel: TLAS walk in entries [0, tlas), a nested BLAS walk above it), by
+    // the rule flatten.cpp builds with (rtb::stack_need), recomputed here from the tables alone;
+    // a cycle is found instead of walked forever (the persistent kernel would spin on it)
+    rtb::StackMemo memo;
+    memo.resize((size_t)s.n_nodes);
+    const int t = rtb::stack_need(s.nodes, s.tlas_root, memo);
     if (t < 0) return fail(RT_ERR_INVALID, "cycle in the TLAS node graph");
     tlas_depth = t + 1;  // + 1 as flatten.cpp records it
     blas_depth = 0;
-    // Each node's need depends only on its subtree, and a completed walk leaves every node it
-    // reached done (colour 2) with its need recorded, so the walks of instance BLASes share
-    // one colour array: a BLAS shared by many instances, or a subtree of one already walked,
-    // costs nothing the second time (O(nodes) in total, not O(instances x nodes)). Likewise
-    // `checked` marks subtrees whose leaves were already found to hold simple primitives.
+    // The walks of instance BLASes share the memo: a BLAS shared by many instances, or a
+    // subtree of one already walked, costs nothing the second time (O(nodes) in total, not
+    // O(instances x nodes)). Likewise `checked` marks subtrees whose leaves were already found
+    // to hold simple primitives.
     std::vector<uint8_t> checked((size_t)s.n_nodes, 0);
     bool simple = true;
     for (int i = 0; i < s.n_instances && simple; ++i) {
         const rt_instance& in = s.instances[i];
         if (in.child_kind != RT_CHILD_BVH) continue;
-        const int b = walk_need(s, in.child, need, colour);
+        const int b = rtb::stack_need(s.nodes, in.child, memo);
         if (b < 0) return fail(RT_ERR_INVALID, "cycle in an instance BVH");
         blas_depth = std::max(blas_depth, b + 1);
         walk(s, in.child, &checked, [](int) {}, [&](Leaf l) {
@@ -230,8 +197,8 @@ int validate(const rt_scene_soa& s, int& tlas_depth, int& blas_depth, int& n_tla
     n_tlas_nodes = 0;
     if (s.n_tlas_nodes > 0 && s.n_tlas_nodes <= s.n_nodes && s.tlas_root == 0) {
         bool inside = true;
-        std::fill(colour.begin(), colour.end(), 0);
-        walk(s, 0, &colour, [&](int i) { inside = inside && i < s.n_tlas_nodes; }, [](Leaf) {});
+        std::vector<uint8_t> seen((size_t)s.n_nodes, 0);
+        walk(s, 0, &seen,[&](int i) { inside = inside && i < s.n_tlas_nodes; }, [](Leaf) {});
         if (inside) n_tlas_nodes = s.n_tlas_nodes;
     }
     return RT_OK;

@@ -1,8 +1,9 @@
 // lower_dump.cpp — what rtl::lower (csrc/scene_lower.cpp) makes of a fixed list of scenes, one
 // JSON line per case: every scalar of rtl::Lowered, the kernel variant its features select, and
 // a 64-bit FNV-1a hash of each of its four tables (over the named fields, never struct padding).
-// Links scene_model.cpp, flatten.cpp and scene_lower.cpp and nothing from HIP; built with ASan
-// and UBSan and compared with tests/golden/lowering.json by tests/test_lowering.py.
+// Links scene_model.cpp, flatten.cpp, bvh_build.cpp and scene_lower.cpp (tests/test_lowering.py
+// LOWERING_SOURCES) and nothing from HIP; built with ASan and UBSan and compared with
+// tests/golden/lowering.json by tests/test_lowering.py.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -458,5 +459,35 @@ int main()
         unbounded_by_reference(w, false);
         dump_world("unbounded_by_reference_times_m1_4", w);
     }
+    // n concentric spheres whose radii span 2^60: no centroid separates them, the SAH peels one
+    // shell per level, and from recursion depth 20 on the builder's median split keeps the walk
+    // within the kernel's 32 stack entries (concentric_200 reaches it, concentric_64 stops short)
+    for (int n : {64, 200}) {
+        World w(1);
+        const int wh = white(w);
+        for (int i = 0; i < n; ++i) w.push(w.sphere(wh, v3(0.0, 0.0, 0.0), std::ldexp(1.0, i % 60) * (1 + i / 60)));
+        dump_world(("concentric_" + std::to_string(n)).c_str(), w);
+    }
+    // every SAH build option set alone (rt_world_set_build_option), on the final scene and the
+    // Cornell smoke scene
+    struct Option {
+        const char* name;
+        void (*set)(rtw::BuildOptions&);
+    };
+    static const Option options[6] = {
+        {"c_isect_0p7", [](rtw::BuildOptions& b) { b.c_isect = 0.7; }},
+        {"max_leaf_2", [](rtw::BuildOptions& b) { b.max_leaf = 2; }},   // 4 changes neither scene
+        {"force_leaf_1", [](rtw::BuildOptions& b) { b.force_leaf = 1; }},
+        {"root_leaf_0", [](rtw::BuildOptions& b) { b.root_leaf = 0; }},
+        {"split_box_pairs_0", [](rtw::BuildOptions& b) { b.split_box_pairs = 0; }},
+        {"split_blas_pairs_0", [](rtw::BuildOptions& b) { b.split_blas_pairs = 0; }},
+    };
+    for (int id : {7, 6})
+        for (const Option& o : options) {
+            World w(1);
+            if (rtw::build_scene(w, id, gradient(), 4, 2)) return 1;
+            o.set(w.build);
+            dump_world(("scene" + std::to_string(id) + "_" + o.name).c_str(), w);
+        }
     return 0;
 }

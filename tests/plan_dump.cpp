@@ -5,8 +5,9 @@
 // then that bound halved down to 1 MiB, each with the ring allowed and ruled out — the attempts
 // run_range's out-of-memory loop can reach. A case may give the camera's shutter ("cam_time0",
 // "cam_time1") and the build's time range ("build_time0", "build_time1"); without them both are
-// [0, 1]. Links scene_model.cpp, flatten.cpp, scene_lower.cpp
-// and launch_plan.cpp and nothing from HIP; built with ASan and UBSan by tests/test_launch_plan.py.
+// [0, 1]. Links the lowering's sources (tests/test_lowering.py LOWERING_SOURCES: scene_model.cpp,
+// flatten.cpp, bvh_build.cpp, scene_lower.cpp) and launch_plan.cpp and nothing from HIP; built with
+// ASan and UBSan by tests/test_launch_plan.py.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>

@@ -3,8 +3,9 @@
 // file in tests/golden/launch_plan.json's format: a line of device facts, then one line per case.
 // Two optional keys beyond plan_dump's: "stack_entries" replaces the lowered scene's traversal
 // stack depth (a deeper scene than any preset), "f32" the precision. Prints one JSON line per case
-// with the decision and the facts it follows from. Links scene_model.cpp, flatten.cpp,
-// scene_lower.cpp and launch_plan.cpp and nothing from HIP; tests/test_seed_stage_plan.py builds
+// with the decision and the facts it follows from. Links the lowering's sources
+// (tests/test_lowering.py LOWERING_SOURCES: scene_model.cpp, flatten.cpp, bvh_build.cpp,
+// scene_lower.cpp) and launch_plan.cpp and nothing from HIP; tests/test_seed_stage_plan.py builds
 // it plain and with ASan and UBSan.
 #include <cstdint>
 #include <cstdio>

@@ -171,7 +171,7 @@ def test_c5_geometry_many_buffer_batches(rt, sched):
 
 @pytest.mark.parametrize("scene_id,W,H,spp", [(0, 1200, 800, 16), (5, 800, 800, 16), (7, 1920, 1080, 8)])
 def test_variants_bit_identical_at_full_size(rt, renderer, scene_id, W, H, spp):
-    """The conservative f32 slab test (boxes padded on the host, flatten.cpp to_f32_box) is a
+    """The conservative f32 slab test (boxes padded on the host, bvh_build.cpp to_f32_box) is a
     claim about rare rays; check it where they occur: whole C2 / C3 / C4 frames (7.7 M to
     16.6 M samples) with f32 vs f64 slabs, LDS vs scratch stack, TLAS in LDS vs L2 — every
     pixel bit for bit."""

@@ -19,14 +19,15 @@ import subprocess
 
 import pytest
 
+from tests.test_lowering import LOWERING_SOURCES
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "rust-ray-tracing-in-a-weekend_amd", "csrc")
 GOLDEN = os.path.join(REPO, "tests", "golden", "launch_plan.json")
 CLANG = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
          "-ffp-contract=off"]
-SOURCES = [os.path.join(REPO, "tests", "plan_dump.cpp")] + \
-          [os.path.join(CSRC, f) for f in ("scene_model.cpp", "flatten.cpp", "scene_lower.cpp", "launch_plan.cpp")]
+SOURCES = [os.path.join(REPO, "tests", "plan_dump.cpp")] + LOWERING_SOURCES + [os.path.join(CSRC, "launch_plan.cpp")]
 MIB = 1 << 20
 POOL, ITEMS, AUTO = 1, 2, 3
 DEFAULTS = dict(spp_chunk=0, row_begin=0, row_stride=1, tile_shard=0, sched=AUTO, prec=0, ring=1, overlap=1,

@@ -23,8 +23,10 @@ GOLDEN = os.path.join(REPO, "tests", "golden", "lowering.json")
 CLANG = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
          "-ffp-contract=off"]
-SOURCES = [os.path.join(REPO, "tests", "lower_dump.cpp")] + \
-          [os.path.join(CSRC, f) for f in ("scene_model.cpp", "flatten.cpp", "scene_lower.cpp")]
+# the HIP-free sources from the scene builders to the lowering (tests/test_launch_plan.py and
+# tests/test_seed_stage_plan.py link them too)
+LOWERING_SOURCES = [os.path.join(CSRC, f) for f in ("scene_model.cpp", "flatten.cpp", "bvh_build.cpp", "scene_lower.cpp")]
+SOURCES = [os.path.join(REPO, "tests", "lower_dump.cpp")] + LOWERING_SOURCES
 
 
 def run_dump(workdir: str) -> str:
@@ -90,6 +92,9 @@ def test_golden_agrees_with_what_the_project_states():
     assert c["instance_beside_tlas_1023"]["stack16_ok"] == 1
     assert [c["sphere_field_%d" % n]["stack16_ok"] for n in (300, 613, 614, 1100)] == [1, 1, 0, 0]
     assert c["sphere_field_leaf31_1038"]["stack16_ok"] == 1 and c["sphere_field_leaf31_1039"]["stack16_ok"] == 0
+    # a stack need of n takes n node levels, so above 21 the SAH build recursed past depth 20, where
+    # its median split (bvh_build.cpp) is what keeps the walk within the kernel's 32 entries
+    assert 21 < c["concentric_200"]["tlas_depth"] <= 32
 
 
 if __name__ == "__main__":

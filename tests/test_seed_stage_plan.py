@@ -14,14 +14,15 @@ import subprocess
 
 import pytest
 
+from tests.test_lowering import LOWERING_SOURCES
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "rust-ray-tracing-in-a-weekend_amd", "csrc")
 GOLDEN = os.path.join(REPO, "tests", "golden", "launch_plan.json")
 CLANG = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
 BASE = ["-std=c++17", "-O1", "-g", "-ffp-contract=off"]
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-SOURCES = [os.path.join(REPO, "tests", "seed_stage_dump.cpp")] + \
-          [os.path.join(CSRC, f) for f in ("scene_model.cpp", "flatten.cpp", "scene_lower.cpp", "launch_plan.cpp")]
+SOURCES = [os.path.join(REPO, "tests", "seed_stage_dump.cpp")] + LOWERING_SOURCES + [os.path.join(CSRC, "launch_plan.cpp")]
 POOL, ITEMS, CHUNKS = 1, 2, 0
 SPHERES = 0            # rtk::FEAT_SET_SPHERES
 WG_THREADS = 768       # RT_BLOCK_SPHERES: the f64 spheres variant's 16-bit-stack workgroup, 12 waves
