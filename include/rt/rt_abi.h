@@ -288,8 +288,27 @@ typedef struct rt_stats {
     int32_t reserved0;           /* always 0 (ABI v4's wavefront-schedule iteration count; that schedule is gone) */
     int64_t ring_bytes;          /* POOL with the in-kernel reduction (ABI v3): its record ring, part of
                                     trace_buf_bytes; 0 when the per-sample buffer ran */
+    /* RT_OPT_PRIMARY_CANDIDATES (additive to ABI v6): the per-pixel candidate table the last render's
+     * new samples took their first hit from; all 0 when the render walked every primary ray */
+    int64_t primary_table_bytes; /* 16 B per image pixel */
+    double primary_build_ms;     /* its build inside this render (0: reused from the context's cache) */
+    double primary_walk_share;   /* share of the image's pixels flagged "walk" (their primary rays walk) */
 } rt_stats;
 int rt_last_stats(rt_ctx* ctx, rt_stats* out);
+
+/* The candidate table of RT_OPT_PRIMARY_CANDIDATES built on the host (no device): for image pixel
+ * (x, y), row 0 = bottom, records[8 * (y * width + x)] is the candidate count n (0xffff: the pixel
+ * is flagged "walk") and the next n entries are leaf slots of the flattened scene (prim_refs[slot]
+ * is the primitive). Every primitive a primary ray of the pixel can hit is in its list, for any
+ * jitter, lens point and ray time of the camera. k_max: candidates before a pixel is flagged. */
+typedef struct rt_primary_candidates_info {
+    int64_t pixels, flagged;     /* pixels of the frame, and those flagged "walk" */
+    int64_t candidates;          /* candidates summed over the pixels not flagged */
+    int32_t max_candidates;      /* the longest list */
+    int32_t slots;               /* candidates a record can hold (7) */
+} rt_primary_candidates_info;
+int rt_primary_candidates_host(const rt_scene_soa* scene, const rt_camera* cam, int width, int height, int k_max,
+                               uint16_t* records, rt_primary_candidates_info* info);
 /* Diagnostic: the raw count_work counters of the last render (n entries; returns how many
  * exist). 0-14 as in rt_stats; wave-cycles (s_memtime) per phase of the pool kernels: 3 ray
  * generation, 4 trace, 5 shading, 8 node loops, 9 leaf tests (both of the top-level walk),
@@ -1103,7 +1122,14 @@ int rt_ctx_set_variant(rt_ctx* ctx, int slab32, int lds_stack, int lds_nodes);
  *                           and the reorder kernel as at any other world size (tests)
  *   RT_OPT_AUTO_DEAL_ORDER  1 (default): whole-frame pool renders are dealt in the cost order the
  *                           render itself measured (rt_last_deal_order); 0: raster order, nothing
- *                           measured; 2: every render measures, none is reordered (A/B runs) */
+ *                           measured; 2: every render measures, none is reordered (A/B runs)
+ *   RT_OPT_PRIMARY_CANDIDATES  1 (default): a new sample of the f64 spheres variant's per-sample pool
+ *                           takes its first hit from an exact test of its pixel's candidate primitives (a
+ *                           table built once per scene upload, camera and frame size inside the render, 16 B
+ *                           per pixel, skipped above 256 MiB) and joins the walk with its first bounce ray;
+ *                           0: every primary ray walks. Same bits either way.
+ *   RT_OPT_PRIMARY_CANDIDATES_K  candidates a pixel's record may hold before the pixel is flagged
+ *                           "walk" (1..7, default 7; tests force 1); takes effect at the next table build */
 enum {
     RT_OPT_TRACE_BUF_BYTES = 1,
     RT_OPT_BATCH_OVERLAP = 2,
@@ -1114,7 +1140,9 @@ enum {
     /* 7, 8: ABI v4's wavefront-schedule options, removed with it (RT_ERR_INVALID) */
     RT_OPT_POOL_RING = 9,
     RT_OPT_COMM_DIRECT = 10,
-    RT_OPT_AUTO_DEAL_ORDER = 11
+    RT_OPT_AUTO_DEAL_ORDER = 11,
+    RT_OPT_PRIMARY_CANDIDATES = 12,
+    RT_OPT_PRIMARY_CANDIDATES_K = 13
 };
 int rt_ctx_set_option(rt_ctx* ctx, int key, int64_t value);
 int rt_ctx_get_option(rt_ctx* ctx, int key, int64_t* value);

@@ -17,6 +17,7 @@
 #include "ctx_internal.hpp"
 #include "deal_cache.hpp"
 #include "launch_plan.hpp"
+#include "primary_candidates.hpp"
 #include "render_internal.hpp"
 #include "scene_lower.hpp"
 #include "trace_kernel.hpp"
@@ -111,6 +112,7 @@ int rt_ctx_create(int device, rt_ctx** out)
     if (e == hipSuccess) e = c->ev_in.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_tr.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_rd.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = c->ev_pc.create();
     if (e == hipSuccess) e = c->counters.alloc(kCounters * sizeof(unsigned long long));
     if (e == hipSuccess) e = c->params.alloc(kParamSlots * sizeof(rtk::KParams));
     if (e == hipSuccess) e = c->work.alloc(2 * rtk::kDealTable * sizeof(unsigned));
@@ -150,6 +152,7 @@ int rt_ctx_upload_soa(rt_ctx* c, const rt_scene_soa* s)
     if (rc) return fail(rc, err);
     c->upload_gen++;   // the scene's tables are replaced below: a measured deal order is another scene's
     c->deal.drop();
+    c->primary_valid = false;
     c->last_deal_n = 0;
 
     struct Table {
@@ -346,6 +349,52 @@ static int deal_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params* p
     return RT_OK;
 }
 
+// RT_OPT_PRIMARY_CANDIDATES: the candidate table of this render's (scene upload, camera, frame size),
+// built here when the key (or the forced k) changed — the cost real use pays, once per key; the one
+// synchronization reads its build time and flagged count — and handed to the launch. Only the f64
+// spheres variant's timed staged per-sample pool kernels read it (trace_launch.hpp picks the
+// CfgPrimary instantiation); any other render, or a frame whose table would exceed
+// rtpc::kMaxTableBytes, walks every primary ray. `stream` already waits for the context's earlier work.
+static int primary_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rtp::Plan& pl, bool count_work,
+                         hipStream_t stream, rtk::KParams& K, rtk::LaunchOpts& o)
+{
+    rt_stats& st = c->stats;
+    st.primary_table_bytes = 0;
+    st.primary_build_ms = 0.0;
+    st.primary_walk_share = 0.0;
+    const size_t bytes = rtpc::table_bytes(p->width, p->height);
+    if (!c->opt_primary || pl.variant != rtk::FEAT_SET_SPHERES || pl.f32 || pl.schedule != RT_SCHED_POOL || !pl.shape.s16 ||
+        pl.seed_stage_bytes == 0 || count_work || bytes > rtpc::kMaxTableBytes || p->width < 2 || p->height < 2)
+        return RT_OK;
+    rtd::Key key = rtd::key_of(c->upload_gen, *cam, *p);
+    key.row_begin = 0;
+    key.row_stride = key.row_block = 1;
+    if (!(c->primary_valid && rtd::same_key(key, c->primary_key) && c->primary_k == c->opt_primary_k)) {
+        c->primary_valid = false;
+        int rc = c->primary_tab.reserve(stream, bytes + 16);
+        if (rc) return rc;
+        unsigned* const flagged = reinterpret_cast<unsigned*>(c->primary_tab.as<char>() + bytes);
+        HIP_TRY(c->ev_pc.record(0, stream));
+        HIP_TRY(rtk::launch_primary_candidates(c->S, *cam, p->width, p->height, c->opt_primary_k, c->primary_tab.p, flagged, stream));
+        HIP_TRY(c->ev_pc.record(1, stream));
+        unsigned n_flagged = 0;
+        HIP_TRY(hipMemcpyAsync(&n_flagged, flagged, sizeof n_flagged, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float ms = 0.0f;
+        HIP_TRY(c->ev_pc.elapsed(0, &ms));
+        c->primary_key = key;
+        c->primary_k = c->opt_primary_k;
+        c->primary_flagged = (int64_t)n_flagged;
+        c->primary_valid = true;
+        st.primary_build_ms = ms;
+    }
+    K.primary = c->primary_tab.as<uint4>();
+    o.primary = 1;
+    st.primary_table_bytes = (int64_t)bytes;
+    st.primary_walk_share = (double)c->primary_flagged / ((double)p->width * (double)p->height);
+    return RT_OK;
+}
+
 // What rt_last_stats shows of a planned range (an empty range: the all-zero plan); the timings,
 // the counters and waves_per_simd are filled when the events resolve.
 static void write_stats(rt_ctx* c, const rtp::Plan& pl, int chunk, int waves_per_simd, bool count)
@@ -450,6 +499,8 @@ int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_
     o.waves_per_simd = &waves_per_simd;
     const rtk::SampleTiles tiles{lay.w, lay.rows, (lay.w + 7) / 8, pl.f32};
     rc = deal_setup(c, cam, p, pl, sink.moments != nullptr, img_tiles, stream, K);
+    if (rc) return rc;
+    rc = primary_setup(c, cam, p, pl, rq.count_work, stream, K, o);
     if (rc) return rc;
 
     if (pl.own_total) HIP_TRY(hipMemsetAsync(acc, 0, pl.px_bytes, stream));
@@ -852,6 +903,14 @@ int rt_ctx_set_option(rt_ctx* c, int key, int64_t v)
         if (v < 0 || v > 2) return fail(RT_ERR_INVALID, "deal order mode out of range (0 off, 1 auto, 2 measure only)");
         c->opt_deal = (int)v;
         return RT_OK;
+    case RT_OPT_PRIMARY_CANDIDATES:
+        if (v < 0 || v > 1) return fail(RT_ERR_INVALID, "primary candidates out of range (0 off, 1 on)");
+        c->opt_primary = (int)v;
+        return RT_OK;
+    case RT_OPT_PRIMARY_CANDIDATES_K:
+        if (v < 1 || v > rtpc::kSlots) return fail(RT_ERR_INVALID, "primary candidates per pixel out of range (1..7)");
+        c->opt_primary_k = (int)v;
+        return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
 }
@@ -869,6 +928,8 @@ int rt_ctx_get_option(rt_ctx* c, int key, int64_t* v)
     case RT_OPT_POOL_RING: *v = c->opt.ring; return RT_OK;
     case RT_OPT_COMM_DIRECT: *v = c->opt_comm_direct; return RT_OK;
     case RT_OPT_AUTO_DEAL_ORDER: *v = c->opt_deal; return RT_OK;
+    case RT_OPT_PRIMARY_CANDIDATES: *v = c->opt_primary; return RT_OK;
+    case RT_OPT_PRIMARY_CANDIDATES_K: *v = c->opt_primary_k; return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
 }

@@ -12,6 +12,7 @@
 #include "rt/rt_abi.h"
 #include "rt/rt_numerics.h"
 #include "ctx_internal.hpp"
+#include "primary_candidates.hpp"
 #include "scene_lower.hpp"
 #include "scene_model.hpp"
 
@@ -309,6 +310,30 @@ int rt_scene_validate(const rt_scene_soa* s, int32_t* tlas_depth, int32_t* blas_
     if (rc) return fail(rc, err);
     if (tlas_depth) *tlas_depth = t;
     if (blas_depth) *blas_depth = b;
+    return RT_OK;
+}
+
+// The primary-candidate table (primary_candidates.hpp) of a flattened scene, built on the host over
+// the tables an upload would give the device (rtl::lower with the pre-leaf hoist): the host twin of
+// what a render builds when RT_OPT_PRIMARY_CANDIDATES is on.
+int rt_primary_candidates_host(const rt_scene_soa* s, const rt_camera* cam, int width, int height, int k_max,
+                               uint16_t* records, rt_primary_candidates_info* info)
+{
+    if (!s || !cam || !records || width < 1 || height < 1 || k_max < 1) return fail(RT_ERR_INVALID, "bad argument");
+    rtl::Lowered L;
+    std::string err;
+    const int rc = rtl::lower(*s, true, L, err);
+    if (rc) return fail(rc, err);
+    static_assert(sizeof(rtpc::Record) == 8 * sizeof(uint16_t), "a record is 8 uint16");
+    const rtpc::TableStats st = rtpc::build_host(L.nodes.data(), L.leaf_prims.data(), s->tlas_root, *cam, width, height, k_max,
+                                                 reinterpret_cast<rtpc::Record*>(records));
+    if (info) {
+        info->pixels = st.pixels;
+        info->flagged = st.flagged;
+        info->candidates = st.candidates;
+        info->max_candidates = st.max_candidates;
+        info->slots = rtpc::kSlots;
+    }
     return RT_OK;
 }
 

@@ -201,6 +201,16 @@ struct rt_ctx {
     rtd::DealCache deal;
     int64_t deal_cap = 0;               // tiles the deal tables behind the work counters hold (trace_kernel.hpp, kDealTable)
     int64_t last_deal_n = 0;            // tiles of the order the last render was dealt in (0: raster; rt_last_deal_order)
+    // RT_OPT_PRIMARY_CANDIDATES (primary_candidates.hpp): the candidate table of the (scene upload, camera,
+    // frame size) it was last built for, kept beside the deal cache's key and dropped with it
+    int opt_primary = 1;                // the option (0: every primary ray walks)
+    int opt_primary_k = 7;              // RT_OPT_PRIMARY_CANDIDATES_K: candidates before a pixel is flagged (tests force 1)
+    DevBuf primary_tab;                 // width x height 16-byte records, then one u32: the pixels flagged "walk"
+    bool primary_valid = false;
+    rtd::Key primary_key;               //   (the row-shard geometry left at its defaults: the table is the frame's)
+    int primary_k = 0;                  //   the k it was built with
+    int64_t primary_flagged = 0;        //   its flagged pixels
+    EventSpan<2> ev_pc;                 //   around its build
 };
 
 // Orders what a call enqueues on `stream` after everything this context enqueued on another

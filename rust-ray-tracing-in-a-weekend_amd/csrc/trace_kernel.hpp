@@ -94,6 +94,10 @@ struct KParams {
     uint32_t deal_div;
     // count_work renders (COUNT kernels): per raster tile of the image, the lane-cycles its samples took
     unsigned long long* tile_cost;
+    // RT_OPT_PRIMARY_CANDIDATES (primary_candidates.hpp): per image pixel (y * img_width + x) the 16-byte
+    // record of the primitives its primary rays can hit; read by trace_pool's CfgPrimary instantiations
+    // only, which the launcher picks when this is set (LaunchOpts.primary). Last: no other field moves.
+    const uint4* primary;
 };
 
 // KParams.tile_major beyond 1, whole-frame renders on the kernels that carry it (trace_pool,
@@ -115,6 +119,7 @@ struct LaunchOpts {
     int count;          // count_work variant
     int pool;           // RT_SCHED_*: 0 chunks, 1 per-sample pool (per-sample output), 2 item pool (partials)
     int f32;            // the f32 fast mode (RT_PREC_F32)
+    int primary = 0;    // KParams.primary is set: the per-sample pool's primary-candidate kernel, where one exists
     int* waves_per_simd = nullptr;  // out (optional): resident waves per SIMD of the launched trace kernel
 };
 
@@ -183,6 +188,10 @@ __host__ __device__ inline size_t tiled_record(int tiles_x, int n_samples, int x
 // radiance, tiled_record order over spp - sample_begin samples; work = one device counter
 hipError_t launch_trace(const SceneDev& S, const KParams& Ph, const KParams* P, double* out,
                         unsigned long long* counters, unsigned* work, const LaunchOpts& o, hipStream_t stream);
+// the primary-candidate table of a camera and frame size over the uploaded scene (primary_candidates.hip):
+// table = width x height 16-byte records, *flagged = the pixels flagged "walk"
+hipError_t launch_primary_candidates(const SceneDev& S, const rt_camera& cam, int width, int height, int k_max, void* table,
+                                     unsigned* flagged, hipStream_t stream);
 // pool schedule: per pixel, chunk sums of its samples (sample order) added to 0.0, scaled to out
 // (out and the carried sums are in pixel order k * width + x)
 hipError_t launch_reduce_samples(const double* samples, void* out, bool f64, SampleTiles g, int n_samples,

@@ -28,6 +28,11 @@ hipError_t launch_variant(const Launch& L, const LaunchOpts& o, hipStream_t stre
                     if constexpr (RT_STAGE_SEEDS != 0 && C::SHAPE.s16)
                         return any_static_lds({(const void*)trace_pool<CfgStage<C>, false>, (const void*)trace_pool<CfgStage<C>, false, true>});
                     else return false;
+                }() ||
+                [] {   // and their primary-candidate forms (timed kernels only)
+                    if constexpr (RT_STAGE_SEEDS != 0 && C::SHAPE.s16 && F == FEAT_SET_SPHERES && !COUNT)
+                        return any_static_lds({(const void*)trace_pool<CfgPrimary<C>, false>, (const void*)trace_pool<CfgPrimary<C>, false, true>});
+                    else return false;
                 }();
             if (static_lds) k = without_stack16(k);
         }
@@ -47,6 +52,10 @@ hipError_t launch_variant(const Launch& L, const LaunchOpts& o, hipStream_t stre
                 if (L.max_waves) nb = std::max(1u, std::min(nb, L.max_waves / (unsigned)wpb));
                 hipLaunchKernelGGL(kernel, dim3(nb), dim3(bt), lds, stream, S, L.P, L.out, L.counters, L.work);
             };
+            if constexpr (RT_STAGE_SEEDS != 0 && C1::SHAPE.s16 && !F32 && F == FEAT_SET_SPHERES && !COUNT) {
+                if (seed_bytes && L.primary)
+                    return go(L.max_waves ? trace_pool<CfgPrimary<C1>, false, true> : trace_pool<CfgPrimary<C1>, false>);
+            }
             if constexpr (RT_STAGE_SEEDS != 0 && C1::SHAPE.s16 && !F32) {
                 if (seed_bytes) return go(L.max_waves ? trace_pool<CfgStage<C1>, false, true> : trace_pool<CfgStage<C1>, false>);
             }

@@ -19,6 +19,7 @@ struct Launch {
     unsigned long long n_blocks;   // 8x8 tiles x chunks
     int* waves_per_simd;           // out (optional): resident blocks per CU = waves per SIMD (4-wave blocks)
     unsigned max_waves = 0;        // per-sample pool with the in-kernel reduction: waves its ring holds
+    bool primary = false;          // KParams.primary is set (LaunchOpts.primary)
 };
 
 // Resident blocks per CU of a kernel (registers, LDS); waves per SIMD reported to the caller.

@@ -133,6 +133,117 @@ __device__ __forceinline__ void ring_reduce(const KParams& P, const double* __re
     }
 }
 
+// New samples resolved from per-pixel candidate lists (CfgPrimary; primary_candidates.hpp, DESIGN.md
+// §5.2). Every primary ray of a pixel lies in a thin double cone, and the primitives that cone can
+// touch are a handful, known per (scene, camera, frame size): KParams.primary holds them per image
+// pixel. A new sample whose pixel is listed takes its closest hit from an exact test of those
+// candidates — the walk's own simple_t and finish_hit, t_max updated as do_leaf does; the closest
+// hit does not depend on the order of the tests — scatters, and joins the walk with its first
+// bounce ray in the same iteration, so a sample holds its lane for one iteration fewer. A flagged
+// pixel's sample (or any at max_depth 0) walks as before. Ray generation in two rejection loops,
+// each under the RT_TRY_LEFT rule: the new samples' disk tries, then the scatter tries of every
+// pending lane, those of this iteration's primary hits included. Each lane's draws keep their order.
+template <class C, bool ITEMS>
+constexpr bool PrimaryPool()
+{
+    static_assert(!C::PRIMARY || (C::STAGE && !C::COUNT && C::F == FEAT_SET_SPHERES && TryLeft<C>()),
+                  "primary candidates: the f64 spheres variant's timed staged kernels");
+    return C::PRIMARY && StagedPool<C, ITEMS>();
+}
+template <class C, class R = typename C::Real>
+__device__ __forceinline__ void generate_primary(const SceneDev& S, const KParams& P, int x, int k, int& depth, bool& new_sample,
+                                                 bool& pending, rt_pstream& st, RayT<R>& r, HitT<R>& h, R& Tr, R& Tg, R& Tb,
+                                                 double& cr, double& cg, double& cb, bool& go, bool& gen_wait, Count& cnt)
+{
+    go = false;
+    if (__any(new_sample)) {   // (wave-uniform)
+        uint4 rec = make_uint4(0xffffu, 0u, 0u, 0u);
+        if (new_sample) {
+            int ix, y;
+            image_xy(P, x, k, ix, y);
+            // (a tile shard's grid is whole 8x8 tiles: an edge tile's lanes beyond the frame have no
+            // record, and walk)
+            if ((unsigned)ix < (unsigned)P.img_width && (unsigned)y < (unsigned)P.height)
+                rec = P.primary[(size_t)y * (size_t)P.img_width + (size_t)ix];
+        }
+        R qx = (R)0, qy = (R)0, qz = (R)0, l2 = (R)1;
+        bool accepted = !new_sample;
+        for (int n = 1;; ++n) {
+            if (!accepted) accepted = unit_try(st, (R)P.scale_m11, false, qx, qy, qz, l2);
+            const uint64_t rejecting = __ballot(!accepted);
+            if (rejecting == 0 || (n >= RT_TRY_MIN && __popcll(rejecting) <= RT_TRY_LEFT)) break;
+        }
+        // the candidates of the lanes whose camera ray is ready and whose pixel is listed
+        unsigned n_cand = 0;
+        if (new_sample && !accepted) {
+            gen_wait = true;   // the jitter stays in r.dx / r.dy, the tries go on in the next iteration
+        } else if (new_sample) {
+            new_sample = false;
+            const R u = r.dx, v = r.dy;
+            camera_end(P, st, u, v, qx, qy, r);
+            const unsigned n = rec.x & 0xffffu;
+            if (n > 7u || depth <= 0) go = true;   // a flagged pixel (0xffff; or depth 0: black, as before): today's path
+            else {
+                finish_ray<C, false>(r, true);   // the sphere part: |d|^2 and its reciprocal
+                n_cand = n + 1;                  // (+ 1: a listed lane with no candidate still ends its sample below)
+            }
+        }
+        if (__any(n_cand != 0)) {
+            const R t_min = (R)0.001;
+            R t_max = (R)RT_INF;
+            HitRefT<R> best;
+            best.sub = 0;
+            best.side = 0;
+            best.prim = -1;
+            // the record's slots (halfwords 1..7) in order: three from the first pair of words, then four
+            uint64_t a = ((uint64_t)rec.y << 32 | (uint64_t)rec.x) >> 16;
+            const uint64_t b = (uint64_t)rec.w << 32 | (uint64_t)rec.z;
+            // as many passes as the longest list among these lanes (wave-uniform: a ballot of the active lanes)
+#pragma unroll 1
+            for (unsigned i = 0; __ballot(i + 1 < n_cand) != 0; ++i) {
+                if (i + 1 < n_cand) {
+                    const int slot = (int)((unsigned)a & 0xffffu);
+                    if (simple_t<C>(S.leaf_prims[slot], r, t_min, t_max, best.t, best.side, cnt, false)) {
+                        best.prim = slot;
+                        t_max = best.t;
+                    }
+                }
+                a >>= 16;
+                if (i == 2) a = b;
+            }
+            if (n_cand != 0) {
+                if (best.prim < 0) {   // main.rs:37: background; the sample ends
+                    cr = cr + Tr * P.bg[0];
+                    cg = cg + Tg * P.bg[1];
+                    cb = cb + Tb * P.bg[2];
+                } else {
+                    finish_hit<C>(S, r, best, h);
+                    pending = shade_begin<C>(S, h, Tr, Tg, Tb, cr, cg, cb);
+                }
+            }
+        }
+    }
+    // the scattered rays of the pending lanes, as the merged loop draws them
+    if (__any(pending)) {
+        R qx = (R)0, qy = (R)0, qz = (R)0, l2 = (R)1;
+        bool accepted = !(pending && shade_draws<C>(S, h.mat));
+        for (int n = 1;; ++n) {
+            if (!accepted) accepted = unit_try(st, (R)P.scale_m11, true, qx, qy, qz, l2);
+            const uint64_t rejecting = __ballot(!accepted);
+            if (rejecting == 0 || (n >= RT_TRY_MIN && __popcll(rejecting) <= RT_TRY_LEFT)) break;
+        }
+        if (pending) {
+            if (!accepted) {
+                gen_wait = true;
+            } else {
+                pending = false;
+                go = shade_end<C, false>(S, h, r, st, Tr, Tg, Tb, qx, qy, qz, l2);
+                if (go) depth -= 1;
+            }
+        }
+    }
+}
+
 // ITEMS (the item pool, default): a unit is a (pixel, chunk) item instead of one sample.
 // The lane that takes it traces the chunk's samples in order, summing their radiance in
 // registers exactly as trace_chunks does, and writes one partial per (pixel, chunk) when
@@ -461,7 +572,9 @@ __global__ void __launch_bounds__(BlockThreads<C>(), min_waves<C>()) trace_pool(
         // Each lane's draws keep their order (its stream is its own), so the bits do not change.
         bool go = true;   // the lane traces this iteration
         bool gen_wait = false;   // RT_TRY_LEFT: the lane's tries go on in the next iteration
-        {
+        if constexpr (PrimaryPool<C, ITEMS>())
+            generate_primary<C>(S, P, x, k, depth, new_sample, pending, st, r, h, Tr, Tg, Tb, cr, cg, cb, go, gen_wait, cnt);
+        if constexpr (!PrimaryPool<C, ITEMS>()) {
             R u = 0, v = 0;
             bool tries = false;
             if (new_sample) {

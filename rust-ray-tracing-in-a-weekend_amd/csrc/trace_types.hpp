@@ -137,6 +137,7 @@ struct Cfg {
     static_assert(SHAPE.s32 == S32_ && SHAPE.lds == LDS_ && SHAPE.nall == NALL_ && SHAPE.f32 == F32_, "the shape of this Cfg");
     using Real = typename std::conditional<F32_, float, double>::type;
     static constexpr bool STAGE = false;   // (CfgStage below)
+    static constexpr bool PRIMARY = false; // (CfgPrimary below)
 };
 // The configuration of trace_pool's staged instantiations (launch_shapes.hpp, RT_STAGE_SEEDS): the
 // wave seeds and jitters a whole row of samples at once. A configuration of its own rather than a
@@ -144,6 +145,14 @@ struct Cfg {
 template <class C>
 struct CfgStage : C {
     static constexpr bool STAGE = true;
+};
+
+// The staged per-sample pool kernel whose new samples take their first hit from their pixel's
+// candidate list (primary_candidates.hpp, KParams.primary; trace_pool.hpp) instead of a walk: the f64
+// spheres variant's timed kernels only. A wrapper like CfgStage, for the same reason.
+template <class C>
+struct CfgPrimary : CfgStage<C> {
+    static constexpr bool PRIMARY = true;
 };
 
 // The configuration of code reached only through an instance or a medium boundary: the

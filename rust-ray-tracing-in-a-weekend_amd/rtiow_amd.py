@@ -52,6 +52,8 @@ RT_OPT_HOIST = 6
 RT_OPT_POOL_RING = 9
 RT_OPT_COMM_DIRECT = 10
 RT_OPT_AUTO_DEAL_ORDER = 11   # 1 (default): whole frames dealt in self-measured cost order; 0 off; 2 measure only
+RT_OPT_PRIMARY_CANDIDATES = 12    # 1 (default): new samples take their first hit from their pixel's candidate list; 0 off
+RT_OPT_PRIMARY_CANDIDATES_K = 13  # candidates per pixel before it is flagged "walk" (1..7, default 7; tests force 1)
 # SAH builder options (rt_world_set_build_option)
 RT_BUILD_C_ISECT = 1
 RT_BUILD_MAX_LEAF = 2
@@ -90,6 +92,7 @@ EXPORTED = [
     "rt_adaptive_state_create", "rt_adaptive_state_destroy", "rt_adaptive_state_advance",
     "rt_adaptive_state_resolve", "rt_adaptive_state_get", "rt_adaptive_state_set",
     "rt_adaptive_state_last_stats", "rt_adaptive_next_group_host",
+    "rt_primary_candidates_host",
 ]
 
 # int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_total)
@@ -160,10 +163,17 @@ class Stats(ctypes.Structure):
                 ("camera_steps", ctypes.c_uint64), ("shade_lanes", ctypes.c_uint64),
                 ("shade_steps", ctypes.c_uint64), ("precision", ctypes.c_int32), ("waves_per_simd", ctypes.c_int32),
                 ("trace_buf_bytes", ctypes.c_int64), ("overlapped", ctypes.c_int32), ("reserved0", ctypes.c_int32),
-                ("ring_bytes", ctypes.c_int64)]
+                ("ring_bytes", ctypes.c_int64),
+                ("primary_table_bytes", ctypes.c_int64), ("primary_build_ms", ctypes.c_double),
+                ("primary_walk_share", ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PrimaryCandidatesInfo(ctypes.Structure):
+    _fields_ = [("pixels", ctypes.c_int64), ("flagged", ctypes.c_int64), ("candidates", ctypes.c_int64),
+                ("max_candidates", ctypes.c_int32), ("slots", ctypes.c_int32)]
 
 
 class CommStats(ctypes.Structure):
@@ -423,6 +433,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_tiles_assemble": ([P, P, ctypes.c_int64, I, ctypes.POINTER(RenderParams), P], I),
         "rt_tiles_assemble_host": ([P, ctypes.c_int64, I, I, I, I, P, P], I),
         "rt_cost_tile_order": ([P, ctypes.c_int64, P], I),
+        "rt_primary_candidates_host": ([ctypes.POINTER(SceneSoA), ctypes.POINTER(Camera), I, I, I, P,
+                                        ctypes.POINTER(PrimaryCandidatesInfo)], I),
         "rt_render_adaptive": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
                                 ctypes.POINTER(AdaptiveParams), ctypes.POINTER(AdaptiveOut)], I),
         "rt_render_adaptive_halves": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
@@ -597,6 +609,16 @@ def validate_soa(soa: SceneSoA):
     t, b = ctypes.c_int32(), ctypes.c_int32()
     _check(lib.rt_scene_validate(ctypes.byref(soa), ctypes.byref(t), ctypes.byref(b)), "rt_scene_validate")
     return t.value, b.value
+
+
+def primary_candidates_host(soa: SceneSoA, cam: Camera, width: int, height: int, k_max: int = 7):
+    """rt_primary_candidates_host: (records (height, width, 8) uint16 — [..., 0] the candidate count or
+    0xffff for a pixel flagged "walk", then leaf slots — and the table's PrimaryCandidatesInfo)."""
+    rec = np.zeros((height, width, 8), dtype=np.uint16)
+    info = PrimaryCandidatesInfo()
+    _check(load_library().rt_primary_candidates_host(ctypes.byref(soa), ctypes.byref(cam), width, height, k_max,
+                                                     rec.ctypes.data, ctypes.byref(info)), "rt_primary_candidates_host")
+    return rec, info
 
 
 def camera_new(look_from, look_at, vup, vfov, aspect_ratio, aperture, focus_dist, time0, time1) -> Camera:
