@@ -43,6 +43,10 @@
  *                             scales supplying the low frequencies its window cannot see
  *   rt_adaptive_state_*       (new) rt_render_adaptive's accumulators kept between calls: the frame
  *                             tightened, previewed, checkpointed, or steered by a caller's error map
+ *   rt_trace_rays             (new) hit_hittables (hittable.rs:43-55) for rays the caller states:
+ *                             the closest hit's record, or whether anything is hit at all
+ *   rt_camera_rays            (new) Camera::get_ray (camera.rs:58-66) for every pixel of a frame,
+ *                             written out as the rays rt_render shoots
  *
  * Threading: a context is bound to one device and is used by one host thread at
  * a time. Worlds are plain host objects.
@@ -1079,6 +1083,118 @@ typedef struct rt_pyramid_stats {
     int64_t scratch_bytes;   /* level scratch that call used: 0 exactly when levels == 1 */
 } rt_pyramid_stats;
 int rt_pyramid_last_stats(rt_ctx* ctx, rt_pyramid_stats* out);
+
+/* ---- ray queries: closest hit and occlusion of caller rays (additive to ABI v6: new symbols only) --
+ * The walk rt_render makes for its own rays, for rays the caller states: one cast per ray, nothing
+ * scatters, no path value is drawn. One GPU, f64.
+ *
+ * Closest. RT_QUERY_CLOSEST is hit_hittables(world, ray, t_min, t_max) (hittable.rs:43-55) and the
+ * HitRecord of the closest primitive. The two interval ends are handed to every primitive test
+ * unchanged, so every interval edge case is whatever that test does with them (hittable.rs:254-273,
+ * 308-320, 417-473). With t_min = 0.001, t_max = +inf, bounce = 0 and the key (pixel, sample) it is
+ * the cast rt_render and rt_render_features make for that pixel's sample, bit for bit
+ * (rt_camera_rays writes those rays). Closest hit does not depend on the order of the tests, and
+ * the one draw of a cast, a constant medium's, is keyed by (seed, key_pixel, key_sample, bounce): the
+ * bits of a ray's result depend on that ray and the scene alone — not on the launch, the order of
+ * the rays in the array, the batches a call is taken in, the acceleration structure or the kernel
+ * variant.
+ *   t       in units of d (d is not normalised, as the reference's); +inf: a miss
+ *   p, n    the record's point and normal: n against the ray (set_face_normal), both mapped back
+ *           through translate / rotate_y as the reference maps them; a medium's hit keeps the
+ *           record's (1, 0, 0); a miss: zeros
+ *   prim    index in rt_scene_soa.prims of the top-level primitive; -1 on a miss
+ *   inner   the geometric primitive behind t: prim itself, the child or BLAS primitive of an
+ *           instance, the boundary of a medium (through the boundary's instance, if it has one; a
+ *           boundary that is a BVH is a set, and inner is then one primitive of it — which one
+ *           depends on the acceleration structure, the one field of a record that does); -1 on a miss
+ *   mat     the material index the record carries (a medium: its phase function); -1 on a miss
+ *   flags   RT_HIT_FRONT: the record's front_face; RT_HIT_MEDIUM: the record is a constant medium's
+ *   albedo  (rt_query_out.albedo) the colour rt_render_features' albedo names for the record; a
+ *           miss: zeros (not a background: a query has none)
+ *
+ * Any. RT_QUERY_ANY answers "RT_QUERY_CLOSEST with the same ray would report a hit", the medium's
+ * keyed draw included: occluded[i] = 1 or 0. The walk stops at the first test that accepts.
+ *
+ * Invalid rays. A ray is not walked, its record is t = NaN, flags = RT_HIT_INVALID and zeros
+ * (prim, inner, mat = -1; the key echoed), its albedo zeros and its occluded byte 0, when
+ *   - a component of o or d, or time, is not finite, or d is (0, 0, 0);
+ *   - t_min or t_max is NaN, or t_min > t_max;
+ *   - the scene holds a moving sphere and time is outside the scene's [time_lo, time_hi]
+ *     (rt_scene_soa: the node boxes bound the spheres for those times only);
+ *   - |o| has a component beyond the bound the launch was planned with (below).
+ * A few compares per ray before anything is walked; no other ray is affected.
+ *
+ * Slab tests. The conservative f32 node tests (rt_ctx_set_variant) hold while ray origins stay
+ * within 2 * rt_scene_soa.pad_extent. Host-pointer calls take the largest |o component| of the valid
+ * rays themselves and plan with it: they flag no ray for its origin. Device-pointer calls plan with
+ * origin_bound, and flag every ray with an |o component| beyond it; 0 or a non-finite value means
+ * unknown: f64 node tests, no ray flagged for its origin. The f32 node tests also need the ray's
+ * largest |d component| within [2^-40, 2^40] (they hold 1/d in f32): a host-pointer call with a
+ * valid ray outside takes the f64 tests; a device-pointer call planned with f32 tests flags such a
+ * ray. rt_query_stats.slab32 says which tests ran; the bits do not depend on it.
+ *
+ * Call errors. A null ctx, params, rays or out; n < 0 or n > 2^31 - 1; a mode other than the two;
+ * CLOSEST with hits and albedo both NULL or with occluded set; ANY with occluded NULL or with hits
+ * or albedo set; on_device with rays or hits not 16-byte aligned: RT_ERR_INVALID. No uploaded scene:
+ * RT_ERR_NO_SCENE. RT_PREC_F32 contexts: RT_ERR_UNSUPPORTED. n = 0 is RT_OK and launches nothing.
+ * Host pointers: the call is synchronous, and takes the rays in batches whose device copies (rays
+ * and results) stay within RT_OPT_TRACE_BUF_BYTES. on_device: the pointers are device pointers and
+ * the call is only enqueued on stream (or the context's stream), like rt_render.
+ * The kernel is trace_query (one instantiation per kernel variant and mode, picked as rt_render's),
+ * one lane per ray. */
+typedef struct rt_ray {            /* 80 B; arrays of them 16-byte aligned on the device */
+    double o[3], d[3];             /* origin, direction (not normalised: t is in units of d) */
+    double time;                   /* the ray's time (moving spheres) */
+    double t_min, t_max;           /* hit_hittables' interval */
+    uint32_t key_pixel, key_sample;/* coordinates of the constant medium's keyed draw for this ray */
+} rt_ray;
+
+enum { RT_HIT_FRONT = 1, RT_HIT_MEDIUM = 2, RT_HIT_INVALID = 4 };
+typedef struct rt_hit {            /* 80 B */
+    double t;                      /* +inf: a miss; NaN: RT_HIT_INVALID */
+    double p[3], n[3];
+    int32_t prim, inner, mat, flags;
+    uint32_t key_pixel, key_sample;/* echoed from the ray, so shuffled or tiled results identify themselves */
+} rt_hit;
+
+enum { RT_QUERY_CLOSEST = 0, RT_QUERY_ANY = 1 };
+typedef struct rt_query_params {
+    int64_t n;                     /* rays */
+    int32_t mode;                  /* RT_QUERY_* */
+    int32_t on_device;             /* 0: host pointers, synchronous; 1: device pointers, only enqueued on stream */
+    uint64_t seed;                 /* the keyed draw's seed (rt_render_params.render_seed's role) */
+    uint32_t bounce;               /* the keyed draw's bounce coordinate; 0 = a primary ray's cast */
+    double origin_bound;           /* on_device: the caller's bound on |o| components; host pointers: ignored */
+    void* stream;
+} rt_query_params;
+typedef struct rt_query_out {
+    rt_hit* hits;                  /* CLOSEST: n records, or NULL */
+    double* albedo;                /* CLOSEST: n x 3, or NULL */
+    uint8_t* occluded;             /* ANY: n bytes */
+} rt_query_out;
+int rt_trace_rays(rt_ctx* ctx, const rt_query_params* p, const rt_ray* rays, const rt_query_out* out);
+
+typedef struct rt_query_stats {
+    double kernel_ms;              /* last rt_trace_rays: its trace_query launches (HIP events; waits for them
+                                      if the call was only enqueued) */
+    int64_t rays;
+    int64_t invalid;               /* host-pointer calls: records flagged RT_HIT_INVALID (ANY: rays the host's
+                                      own statement of the rules above flags); device-pointer calls: -1 */
+    int32_t variant_features;      /* the kernel variant's feature set, as rt_stats.variant_features */
+    int32_t slab32;                /* 1: the launches tested f32 node slabs */
+    int32_t mode, batches;         /* RT_QUERY_*; launches the call took */
+} rt_query_stats;
+int rt_query_last_stats(rt_ctx* ctx, rt_query_stats* out);
+
+/* The ray rt_render shoots for every pixel's sample `sample` under render_seed (Camera::get_ray,
+ * camera.rs:58-66, after main.rs:517-518's jitter: the path stream of (pixel, sample), its two jitter
+ * draws, random_in_unit_disk's tries, the time draw), host code with no context: out[i] has that
+ * origin, direction and time, t_min = 0.001, t_max = +inf and the key (y * width + x, sample).
+ * tiled = 0: ray i is pixel i (row 0 at the bottom). tiled = 1: 8x8 tiles in tile-grid order,
+ * row-major inside a tile, pixels past the image left out (the lane order of the chunk kernels);
+ * still width * height records. width, height >= 2, width * height <= 2^31 - 1, sample >= 0. */
+int rt_camera_rays(const rt_camera* cam, int width, int height, uint64_t render_seed, int sample, int tiled,
+                   rt_ray* out);
 
 /* ---- output ------------------------------------------------------------------------------ */
 /* P3 PPM byte for byte as the reference writes it (write_color, math.rs:119-132; main.rs:472,

@@ -14,6 +14,7 @@
 
 #include "rt/rt_abi.h"
 #include "rt/rt_numerics.h"
+#include "camera_rays.hpp"
 #include "ctx_internal.hpp"
 #include "deal_cache.hpp"
 #include "launch_plan.hpp"
@@ -104,6 +105,7 @@ int rt_ctx_create(int device, rt_ctx** out)
     if (e == hipSuccess) e = c->ev.create();
     if (e == hipSuccess) e = c->flt_denoise.ev.create();
     if (e == hipSuccess) e = c->ev_ft.create();
+    if (e == hipSuccess) e = c->ev_q.create();
     if (e == hipSuccess) e = c->flt_atrous.ev.create();
     if (e == hipSuccess) e = c->flt_cross.ev.create();
     if (e == hipSuccess) e = c->flt_pyramid.ev.create();
@@ -242,12 +244,13 @@ int fill_kparams(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, con
     std::memset(&K, 0, sizeof K);
     K.cam = *cam;
     for (int i = 0; i < 3; ++i) K.bg[i] = p->background[i];
-    K.scale_m11 = rt_uniform_incl_scale(-1.0, 1.0);
-    K.scale_time = rt_uniform_incl_scale(cam->time0, cam->time1);
-    K.wm1 = (double)p->width - 1.0;
-    K.hm1 = (double)p->height - 1.0;
-    K.inv_wm1 = 1.0 / K.wm1;
-    K.inv_hm1 = 1.0 / K.hm1;
+    const rtc::CameraScales cs = rtc::camera_scales(*cam, p->width, p->height);   // (camera_rays.hpp: rt_camera_rays' too)
+    K.scale_m11 = cs.scale_m11;
+    K.scale_time = cs.scale_time;
+    K.wm1 = cs.wm1;
+    K.hm1 = cs.hm1;
+    K.inv_wm1 = cs.inv_wm1;
+    K.inv_hm1 = cs.inv_hm1;
     K.seed = p->render_seed;
     K.width = lay.w;
     K.height = p->height;

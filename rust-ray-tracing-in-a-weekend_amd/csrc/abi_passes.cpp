@@ -1,15 +1,17 @@
 // abi_passes.cpp — the auxiliary passes behind the C ABI (include/rt/rt_abi.h) that render through
-// the driver (render_internal.hpp): tile-adaptive sampling and the first-hit feature buffers, with
-// their stats.
+// the driver (render_internal.hpp): tile-adaptive sampling, the first-hit feature buffers and the
+// ray queries, with their stats.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "rt/rt_abi.h"
 #include "adaptive_criterion.hpp"
 #include "adaptive_frame.hpp"
 #include "ctx_internal.hpp"
 #include "features_kernel.hpp"
+#include "query_kernel.hpp"
 #include "render_internal.hpp"
 
 extern "C" {
@@ -242,6 +244,188 @@ int rt_features_last_stats(rt_ctx* c, rt_features_stats* out)
         c->fstats.reduce_ms = ms[1];
     }
     *out = c->fstats;
+    return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- ray queries (rt_abi.h; query_device.hpp, query_kernel.hip) ---------------------------------
+// The host's statement of "Invalid rays" (rt_abi.h) but for the origin bound: what a host-pointer
+// call plans from (the largest |o component| and the |d| range of the rays that will be walked) and
+// the invalid count of a call that brings no records back.
+namespace {
+
+struct RayScan {
+    int64_t invalid = 0;
+    double o_max = 0.0;                  // the largest |o component| of the valid rays
+    bool d_in_f32_range = true;          // every valid ray's largest |d component| is within [2^-40, 2^40]
+};
+
+RayScan scan_rays(const rt_ray* rays, int64_t n, const rtp::SceneFacts& scene)
+{
+    RayScan s;
+    for (int64_t i = 0; i < n; ++i) {
+        const rt_ray& r = rays[i];
+        bool ok = std::isfinite(r.time);
+        for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(r.o[a]) && std::isfinite(r.d[a]);
+        const double dm = std::fmax(std::fmax(std::fabs(r.d[0]), std::fabs(r.d[1])), std::fabs(r.d[2]));
+        ok = ok && dm > 0.0 && r.t_min <= r.t_max;
+        if (scene.has_moving) ok = ok && r.time >= scene.time_lo && r.time <= scene.time_hi;
+        if (!ok) {
+            s.invalid++;
+            continue;
+        }
+        s.o_max = std::fmax(s.o_max, std::fmax(std::fmax(std::fabs(r.o[0]), std::fabs(r.o[1])), std::fabs(r.o[2])));
+        s.d_in_f32_range = s.d_in_f32_range && dm >= 0x1.0p-40 && dm <= 0x1.0p+40;
+    }
+    return s;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The launch is planned as a chunk-schedule launch is (rtp::plan: the kernel variant, the slab
+// precision, what is staged in LDS), with the rays' origin bound in the camera's place. Device
+// pointers: one launch on the caller's arrays, timed by ev_q. Host pointers: batches of rays whose
+// device copies — the rays, then each output — fit RT_OPT_TRACE_BUF_BYTES, in the context's query
+// buffer; each batch is copied in, traced between ev_q's two events and copied back, and the
+// batches' kernel times add up.
+int rt_trace_rays(rt_ctx* c, const rt_query_params* p, const rt_ray* rays, const rt_query_out* out)
+{
+    if (!c || !p || !rays || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (p->mode != RT_QUERY_CLOSEST && p->mode != RT_QUERY_ANY) return fail(RT_ERR_INVALID, "rt_query_params.mode");
+    const bool any = p->mode == RT_QUERY_ANY;
+    if (!any && ((!out->hits && !out->albedo) || out->occluded))
+        return fail(RT_ERR_INVALID, "RT_QUERY_CLOSEST writes hits or albedo (at least one) and no occluded bytes");
+    if (any && (!out->occluded || out->hits || out->albedo))
+        return fail(RT_ERR_INVALID, "RT_QUERY_ANY writes occluded bytes only");
+    if (p->n < 0 || p->n > 0x7fffffffLL) return fail(RT_ERR_INVALID, "rt_query_params.n: 0 .. 2^31 - 1 rays");
+    const bool on_dev = p->on_device != 0;
+    if (on_dev && (((uintptr_t)rays & 15) || ((uintptr_t)out->hits & 15)))
+        return fail(RT_ERR_INVALID, "device ray and hit records must be 16-byte aligned");
+    if (!c->has_scene) return fail(RT_ERR_NO_SCENE, "no scene uploaded");
+    if (c->opt.precision == RT_PREC_F32) return fail(RT_ERR_UNSUPPORTED, "ray queries in the f32 mode");
+    const int64_t n = p->n;
+    c->ev_q.disarm();
+    c->qstats = rt_query_stats{};
+    c->qstats.mode = p->mode;
+    c->qstats.invalid = on_dev ? -1 : 0;
+    if (n == 0) return RT_OK;
+
+    // the origin bound the launch is planned with, and whether every |d| suits f32 slabs
+    RayScan scan;
+    double bound = p->origin_bound;
+    const bool bound_known = on_dev ? std::isfinite(bound) && bound > 0.0 : true;
+    if (!on_dev) {
+        scan = scan_rays(rays, n, c->scene);
+        bound = scan.o_max;
+    }
+    rtp::Options opt = c->opt;
+    opt.schedule = RT_SCHED_CHUNKS;
+    if (!bound_known || !scan.d_in_f32_range) opt.slab32 = 0;
+    rtp::Request rq;
+    rq.lay = Layout{8, 8};
+    rq.s_begin = 0;
+    rq.s_end = 1;
+    rq.chunk = 1;
+    rq.cam_mag = bound_known ? bound : 0.0;
+    rq.cam_time0 = c->scene.time_lo;   // (ray times are checked per ray, in the kernel)
+    rq.cam_time1 = c->scene.time_hi;
+    // The query's walk tests every instance where it meets it, its BLAS walk nested at blas_base;
+    // the scene's stack_entries may be the trace kernels' smaller count, which relies on their
+    // deferred first instance. So the launch is planned (LDS or scratch stack, the LDS left for
+    // BLAS nodes) and laid out with the entries of the nested walk.
+    rtp::SceneFacts facts = c->scene;
+    facts.stack_entries = facts.nested_stack_entries;
+    const rtp::Plan pl = rtp::plan(facts, c->dev, opt, rq, rtp::Retry{c->sample_buf_cap, false});
+    if (pl.err) return fail(pl.err, pl.err_msg);
+    PlannedLaunch launch = planned_launch(c->S, pl);
+    launch.S.stack_entries = facts.stack_entries;
+
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = p->stream ? (hipStream_t)p->stream : c->stream;
+    StreamScope scope(c, stream);
+    int rc = scope.begin();
+    if (rc) return rc;
+
+    rtk::QueryArgs Q{};
+    Q.seed = p->seed;
+    Q.bounce = p->bounce;
+    Q.has_moving = c->scene.has_moving;
+    Q.time_lo = c->scene.time_lo;
+    Q.time_hi = c->scene.time_hi;
+    Q.origin_bound = bound_known ? bound : (double)INFINITY;
+    c->qstats.rays = n;
+    c->qstats.variant_features = (int32_t)pl.variant;
+    c->qstats.slab32 = pl.slab32;
+
+    if (on_dev) {
+        Q.rays = rays;
+        Q.hits = out->hits;
+        Q.albedo = out->albedo;
+        Q.occluded = out->occluded;
+        Q.n = n;
+        HIP_TRY(c->ev_q.record(0, stream));
+        HIP_TRY(rtk::launch_query(launch.S, Q, p->mode, launch.o, stream));
+        HIP_TRY(c->ev_q.record(1, stream));
+        c->ev_q.arm();
+        c->qstats.batches = 1;
+        return scope.end();
+    }
+
+    // a batch's device copies: [rays][hits][albedo][occluded], each on a 256-byte boundary
+    const size_t per_ray = sizeof(rt_ray) + (out->hits ? sizeof(rt_hit) : 0) + (out->albedo ? 3 * sizeof(double) : 0) + (any ? 1 : 0);
+    const int64_t batch = (int64_t)std::min<size_t>((size_t)n, std::max<size_t>(1, c->sample_buf_cap / per_ray));
+    const size_t off_hits = align_up((size_t)batch * sizeof(rt_ray), 256);
+    const size_t off_albedo = off_hits + (out->hits ? align_up((size_t)batch * sizeof(rt_hit), 256) : 0);
+    const size_t off_occ = off_albedo + (out->albedo ? align_up((size_t)batch * 3 * sizeof(double), 256) : 0);
+    rc = c->query_buf.reserve(stream, off_occ + (any ? align_up((size_t)batch, 256) : 0));
+    if (rc) return rc;
+    char* const base = c->query_buf.as<char>();
+    Q.rays = reinterpret_cast<const rt_ray*>(base);
+    Q.hits = out->hits ? reinterpret_cast<rt_hit*>(base + off_hits) : nullptr;
+    Q.albedo = out->albedo ? reinterpret_cast<double*>(base + off_albedo) : nullptr;
+    Q.occluded = any ? reinterpret_cast<uint8_t*>(base + off_occ) : nullptr;
+    double kernel_ms = 0.0;
+    for (int64_t b0 = 0; b0 < n; b0 += batch) {
+        const size_t m = (size_t)std::min<int64_t>(batch, n - b0);
+        Q.n = (long long)m;
+        HIP_TRY(hipMemcpyAsync(base, rays + b0, m * sizeof(rt_ray), hipMemcpyHostToDevice, stream));
+        HIP_TRY(c->ev_q.record(0, stream));
+        HIP_TRY(rtk::launch_query(launch.S, Q, p->mode, launch.o, stream));
+        HIP_TRY(c->ev_q.record(1, stream));
+        if (out->hits) HIP_TRY(hipMemcpyAsync(out->hits + b0, Q.hits, m * sizeof(rt_hit), hipMemcpyDeviceToHost, stream));
+        if (out->albedo) HIP_TRY(hipMemcpyAsync(out->albedo + 3 * b0, Q.albedo, m * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (any) HIP_TRY(hipMemcpyAsync(out->occluded + b0, Q.occluded, m, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));   // the next batch reuses the buffer
+        float ms = 0.0f;
+        HIP_TRY(c->ev_q.elapsed(0, &ms));
+        kernel_ms += ms;
+        c->qstats.batches++;
+    }
+    rc = scope.end();
+    if (rc) return rc;
+    c->qstats.kernel_ms = kernel_ms;
+    c->qstats.invalid = scan.invalid;
+    if (out->hits) {   // counted from the flags that came back
+        c->qstats.invalid = 0;
+        for (int64_t i = 0; i < n; ++i) c->qstats.invalid += (out->hits[i].flags & RT_HIT_INVALID) != 0;
+    }
+    return RT_OK;
+}
+
+int rt_query_last_stats(rt_ctx* c, rt_query_stats* out)
+{
+    if (!c || !out) return fail(RT_ERR_INVALID, "null argument");
+    if (c->ev_q.pending) {
+        HIP_TRY(hipSetDevice(c->device));
+        float ms[1] = {0};
+        const int rc = c->ev_q.resolve(ms);
+        if (rc) return rc;
+        c->qstats.kernel_ms = ms[0];
+    }
+    *out = c->qstats;
     return RT_OK;
 }
 

@@ -169,6 +169,9 @@ struct rt_ctx {
     FilterSlot<rt_denoise_stats> flt_denoise;   // rt_denoise, rt_denoise_guided: no scratch
     rt_features_stats fstats{};         // the last rt_render_features (rt_features_last_stats)
     EventSpan<3> ev_ft;                 //   before its trace launches, after them, after its reductions
+    rt_query_stats qstats{};            // the last rt_trace_rays (rt_query_last_stats)
+    EventSpan<2> ev_q;                  //   around a launch of trace_query
+    DevBuf query_buf;                   //   a host-pointer call's device copies: a batch's rays, then its results
     FilterSlot<rt_atrous_stats> flt_atrous;     // rt_denoise_atrous: its state between levels (rtk::AtrousRec)
     FilterSlot<rt_cross_stats> flt_cross;       // rt_denoise_cross: e(p) between its two kernels (f64 per pixel; only with stderr_out)
     FilterSlot<rt_pyramid_stats> flt_pyramid;   // rt_denoise_pyramid: its levels' f64 frames (rtk::PyramidLayout; none at one level)

@@ -91,6 +91,7 @@ SceneFacts scene_facts(const rtl::Lowered& L, const rt_scene_soa& s)
     f.n_nodes = s.n_nodes;
     f.n_blas_bfs = L.n_blas_bfs;
     f.stack_entries = L.stack_entries;
+    f.nested_stack_entries = L.blas_base + (L.blas_depth > 0 ? L.blas_depth + 1 : 0);
     f.stack16_ok = L.stack16_ok;
     f.n_materials = s.n_materials;
     f.n_textures = s.n_textures;

@@ -34,6 +34,10 @@ struct SceneFacts {   // what the context keeps of an uploaded scene
     int n_tlas_nodes = 0;
     int n_nodes = 0;            // BVH nodes of the scene (TLAS + BLASes)
     int n_blas_bfs = 0, stack_entries = 0, stack16_ok = 0;   // rtl::Lowered's fields of these names
+    // the entries of a walk that nests every BLAS walk in the top-level one, deferring none
+    // (stack_entries may count on the trace kernels' deferred first instance: scene_lower.cpp);
+    // rt_trace_rays' launches are planned and laid out with it
+    int nested_stack_entries = 0;
     int n_materials = 0, n_textures = 0;
     double pad_extent = 0.0;
     // the scene holds a moving sphere, whose boxes bound it for ray times in [time_lo, time_hi]

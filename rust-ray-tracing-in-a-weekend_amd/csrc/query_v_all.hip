@@ -1,0 +1,7 @@
+// query_v_all.hip — instantiates rt_trace_rays' kernels (query_device.hpp) for one feature set
+// (FEAT_ALL); each variant is its own translation unit so the build compiles them in parallel.
+#include "query_device.hpp"
+
+namespace rtk {
+template hipError_t launch_query_variant<FEAT_ALL>(const SceneDev&, const QueryArgs&, int, const LaunchOpts&, hipStream_t);
+}  // namespace rtk

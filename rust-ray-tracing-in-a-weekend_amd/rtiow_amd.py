@@ -93,6 +93,7 @@ EXPORTED = [
     "rt_adaptive_state_resolve", "rt_adaptive_state_get", "rt_adaptive_state_set",
     "rt_adaptive_state_last_stats", "rt_adaptive_next_group_host",
     "rt_primary_candidates_host",
+    "rt_trace_rays", "rt_query_last_stats", "rt_camera_rays",
 ]
 
 # int (*rt_progress_fn)(void* user, int64_t samples_done, int64_t samples_total)
@@ -285,6 +286,36 @@ class FeaturesStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# rt_ray and rt_hit as numpy record dtypes (80 bytes each, the C structs' offsets)
+RAY = np.dtype([("o", "<f8", (3,)), ("d", "<f8", (3,)), ("time", "<f8"), ("t_min", "<f8"), ("t_max", "<f8"),
+                ("key_pixel", "<u4"), ("key_sample", "<u4")])
+HIT = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("n", "<f8", (3,)), ("prim", "<i4"), ("inner", "<i4"), ("mat", "<i4"),
+                ("flags", "<i4"), ("key_pixel", "<u4"), ("key_sample", "<u4")])
+RT_HIT_FRONT, RT_HIT_MEDIUM, RT_HIT_INVALID = 1, 2, 4
+RT_QUERY_CLOSEST, RT_QUERY_ANY = 0, 1
+
+
+class QueryParams(ctypes.Structure):
+    """rt_query_params."""
+    _fields_ = [("n", ctypes.c_int64), ("mode", ctypes.c_int32), ("on_device", ctypes.c_int32), ("seed", ctypes.c_uint64),
+                ("bounce", ctypes.c_uint32), ("origin_bound", ctypes.c_double), ("stream", ctypes.c_void_p)]
+
+
+class QueryOut(ctypes.Structure):
+    """rt_query_out: CLOSEST hits and / or albedo, ANY occluded."""
+    _fields_ = [("hits", ctypes.c_void_p), ("albedo", ctypes.c_void_p), ("occluded", ctypes.c_void_p)]
+
+
+class QueryStats(ctypes.Structure):
+    """rt_query_stats: the last rt_trace_rays of a context."""
+    _fields_ = [("kernel_ms", ctypes.c_double), ("rays", ctypes.c_int64), ("invalid", ctypes.c_int64),
+                ("variant_features", ctypes.c_int32), ("slab32", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("batches", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DenoiseGuides(ctypes.Structure):
     """rt_denoise_guides: the guide frames (any may be null) and their sigmas."""
     _fields_ = [("albedo", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("depth", ctypes.c_void_p),
@@ -448,6 +479,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_render_features": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
                                 ctypes.POINTER(FeaturesOut)], I),
         "rt_features_last_stats": ([P, ctypes.POINTER(FeaturesStats)], I),
+        "rt_trace_rays": ([P, ctypes.POINTER(QueryParams), P, ctypes.POINTER(QueryOut)], I),
+        "rt_query_last_stats": ([P, ctypes.POINTER(QueryStats)], I),
+        "rt_camera_rays": ([ctypes.POINTER(Camera), I, I, U64, I, I, P], I),
         "rt_denoise_guided": ([P, ctypes.POINTER(DenoiseParams), P, P, ctypes.POINTER(DenoiseGuides), P], I),
         "rt_denoise_guided_host": ([ctypes.POINTER(DenoiseParams), P, P, ctypes.POINTER(DenoiseGuides), P], I),
         "rt_denoise_atrous": ([P, ctypes.POINTER(AtrousParams), P, P, ctypes.POINTER(DenoiseGuides), P, P], I),
@@ -619,6 +653,17 @@ def primary_candidates_host(soa: SceneSoA, cam: Camera, width: int, height: int,
     _check(load_library().rt_primary_candidates_host(ctypes.byref(soa), ctypes.byref(cam), width, height, k_max,
                                                      rec.ctypes.data, ctypes.byref(info)), "rt_primary_candidates_host")
     return rec, info
+
+
+def camera_rays(cam: Camera, width: int, height: int, seed: int, sample: int, tiled: bool = False) -> np.ndarray:
+    """rt_camera_rays: the width * height RAY records rt_render shoots for `sample` of every pixel under
+    render seed `seed` (t_min 0.001, t_max inf, key (pixel, sample)); row-major from the bottom row, or
+    (tiled) 8x8 tiles in tile-grid order."""
+    rays = np.zeros(width * height, dtype=RAY)
+    lib = load_library()
+    _check(lib.rt_camera_rays(ctypes.byref(cam), width, height, seed, sample, int(bool(tiled)), rays.ctypes.data),
+           "rt_camera_rays")
+    return rays
 
 
 def camera_new(look_from, look_at, vup, vfov, aspect_ratio, aperture, focus_dist, time0, time1) -> Camera:
@@ -1297,6 +1342,36 @@ class Renderer:
 
     def features_stats(self) -> FeaturesStats:
         return _stats(self, "rt_features_last_stats", FeaturesStats)
+
+    def trace_rays(self, rays, mode: int = RT_QUERY_CLOSEST, seed: int = 1, bounce: int = 0, albedo: bool = False):
+        """rt_trace_rays on host arrays. rays: RAY records. CLOSEST: the HIT records, or (albedo) the
+        pair (HIT records, albedo n x 3); ANY: the occluded bytes as a bool array."""
+        rays = np.ascontiguousarray(rays, dtype=RAY)
+        n = rays.shape[0]
+        p = QueryParams(n=n, mode=mode, on_device=0, seed=seed, bounce=bounce)
+        if mode == RT_QUERY_ANY:
+            occ = np.zeros(n, dtype=np.uint8)
+            out = QueryOut(None, None, occ.ctypes.data)
+        else:
+            hits = np.zeros(n, dtype=HIT)
+            alb = np.zeros((n, 3), dtype=np.float64) if albedo else None
+            out = QueryOut(hits.ctypes.data, alb.ctypes.data if albedo else None, None)
+        _check(self.lib.rt_trace_rays(self.h, ctypes.byref(p), rays.ctypes.data, ctypes.byref(out)), "rt_trace_rays")
+        if mode == RT_QUERY_ANY:
+            return occ.astype(bool)
+        return (hits, alb) if albedo else hits
+
+    def trace_rays_device(self, rays_ptr: int, n: int, mode: int = RT_QUERY_CLOSEST, hits_ptr: int = 0, albedo_ptr: int = 0,
+                          occluded_ptr: int = 0, seed: int = 1, bounce: int = 0, origin_bound: float = 0.0,
+                          stream: Optional[int] = None):
+        """Enqueues rt_trace_rays on device arrays (RAY / HIT records 16-byte aligned; 0 leaves an
+        output out) on `stream`. origin_bound: the caller's bound on |origin| components (0: unknown)."""
+        p = QueryParams(n=n, mode=mode, on_device=1, seed=seed, bounce=bounce, origin_bound=origin_bound, stream=stream)
+        out = QueryOut(hits_ptr or None, albedo_ptr or None, occluded_ptr or None)
+        _check(self.lib.rt_trace_rays(self.h, ctypes.byref(p), rays_ptr, ctypes.byref(out)), "rt_trace_rays")
+
+    def query_stats(self) -> QueryStats:
+        return _stats(self, "rt_query_last_stats", QueryStats)
 
     def denoise_stats(self) -> DenoiseStats:
         return _stats(self, "rt_denoise_last_stats", DenoiseStats)
