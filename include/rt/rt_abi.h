@@ -297,6 +297,9 @@ typedef struct rt_stats {
     int64_t primary_table_bytes; /* 16 B per image pixel */
     double primary_build_ms;     /* its build inside this render (0: reused from the context's cache) */
     double primary_walk_share;   /* share of the image's pixels flagged "walk" (their primary rays walk) */
+    /* RT_OPT_SKIP_SKY_TILES (additive to ABI v6) */
+    int64_t sky_tiles;           /* 8x8 tiles the last render did not trace: every pixel of them sees only the
+                                    background (0: the option off, or a render it does not apply to) */
 } rt_stats;
 int rt_last_stats(rt_ctx* ctx, rt_stats* out);
 
@@ -313,6 +316,11 @@ typedef struct rt_primary_candidates_info {
 } rt_primary_candidates_info;
 int rt_primary_candidates_host(const rt_scene_soa* scene, const rt_camera* cam, int width, int height, int k_max,
                                uint16_t* records, rt_primary_candidates_info* info);
+/* The all-sky 8x8 tiles of that table (RT_OPT_SKIP_SKY_TILES; no device): flags[ty * ceil(width / 8) + tx]
+ * is 1 when every pixel of raster tile (tx, ty) within the frame has an empty candidate list (n == 0),
+ * else 0; ceil(width / 8) * ceil(height / 8) bytes. *count (optional) is how many are 1. */
+int rt_primary_sky_tiles_host(const rt_scene_soa* scene, const rt_camera* cam, int width, int height, int k_max,
+                              uint8_t* flags, int64_t* count);
 /* Diagnostic: the raw count_work counters of the last render (n entries; returns how many
  * exist). 0-14 as in rt_stats; wave-cycles (s_memtime) per phase of the pool kernels: 3 ray
  * generation, 4 trace, 5 shading, 8 node loops, 9 leaf tests (both of the top-level walk),
@@ -1245,7 +1253,13 @@ int rt_ctx_set_variant(rt_ctx* ctx, int slab32, int lds_stack, int lds_nodes);
  *                           per pixel, skipped above 256 MiB) and joins the walk with its first bounce ray;
  *                           0: every primary ray walks. Same bits either way.
  *   RT_OPT_PRIMARY_CANDIDATES_K  candidates a pixel's record may hold before the pixel is flagged
- *                           "walk" (1..7, default 7; tests force 1); takes effect at the next table build */
+ *                           "walk" (1..7, default 7; tests force 1); takes effect at the next table build
+ *   RT_OPT_SKIP_SKY_TILES   1 (default): a whole-frame rt_render through the per-sample buffer that has a
+ *                           primary-candidate table and a deal table (RT_OPT_AUTO_DEAL_ORDER 1 or 2),
+ *                           at max_depth >= 1, traces no 8x8 tile whose pixels' candidate lists are all
+ *                           empty: each of their samples is exactly the background, and the reduction
+ *                           sums that constant as it would have summed the records (rt_stats.sky_tiles).
+ *                           0: every tile is traced. Same bits either way. */
 enum {
     RT_OPT_TRACE_BUF_BYTES = 1,
     RT_OPT_BATCH_OVERLAP = 2,
@@ -1258,7 +1272,8 @@ enum {
     RT_OPT_COMM_DIRECT = 10,
     RT_OPT_AUTO_DEAL_ORDER = 11,
     RT_OPT_PRIMARY_CANDIDATES = 12,
-    RT_OPT_PRIMARY_CANDIDATES_K = 13
+    RT_OPT_PRIMARY_CANDIDATES_K = 13,
+    RT_OPT_SKIP_SKY_TILES = 14
 };
 int rt_ctx_set_option(rt_ctx* ctx, int key, int64_t value);
 int rt_ctx_get_option(rt_ctx* ctx, int key, int64_t* value);

@@ -291,13 +291,39 @@ int fill_kparams(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, con
 // tile_major = kDealMeasure; the next one of the key reads the costs back (the one synchronization,
 // inside this call), builds the order and uploads it; later ones only set tile_major =
 // kDealOrdered. `stream` already waits for the context's earlier work.
+// RT_OPT_SKIP_SKY_TILES (sky_ok: this render may leave its all-sky tiles out, c->sky_flags): a render
+// that goes through a table is dealt the table's unflagged tiles only — the identity table and the
+// cost order alike, the cache's own order stays whole — and *dealt_tiles is how many that is. The
+// device tables are written again whenever what they leave out (deal_sky_gen) is not what this
+// render wants, so the option may change between two renders of a key.
 static int deal_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rtp::Plan& pl, bool adaptive_pass,
-                      int64_t img_tiles, hipStream_t stream, rtk::KParams& K)
+                      int64_t img_tiles, bool sky_ok, hipStream_t stream, rtk::KParams& K, int64_t* dealt_tiles)
 {
     c->last_deal_n = 0;
     const bool ok = rtk::deal_variant(pl.variant) && rtd::eligible(*p, pl.schedule, adaptive_pass);
     const rtd::Decision d = c->deal.next(c->opt_deal, ok, rtd::key_of(c->upload_gen, *cam, *p), img_tiles);
     const size_t n = (size_t)img_tiles;
+    const bool sky = sky_ok && (d.measure || d.ordered) && c->sky_flags.size() == n;
+    const uint64_t want_gen = sky ? c->sky_gen : 0;
+    // `order` (n raster tiles by position) without the tiles this render skips, to both tables
+    const auto upload = [&](const uint32_t* order) -> hipError_t {
+        std::vector<uint32_t> live;
+        size_t m = n;
+        if (sky) {
+            live.reserve(n);
+            for (size_t i = 0; i < n; ++i)
+                if (!c->sky_flags[order[i]]) live.push_back(order[i]);
+            order = live.data();
+            m = live.size();
+        }
+        hipError_t e = hipSuccess;
+        for (int h = 0; h < 2 && e == hipSuccess; ++h)
+            e = hipMemcpyAsync(c->work.as<unsigned>() + h * c->work_stride + rtk::kDealTable, order, m * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (the source is pageable, and local when filtered)
+        if (e == hipSuccess) c->deal_sky_gen = want_gen;
+        return e;
+    };
     if (d.measure) {
         if (img_tiles > c->deal_cap) {   // (a key's first render: no work on the context's streams reads them)
             HIP_TRY(hipStreamSynchronize(stream));
@@ -314,12 +340,9 @@ static int deal_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params* p
         }
         std::vector<uint32_t> raster(n);
         for (size_t i = 0; i < n; ++i) raster[i] = (uint32_t)i;
-        for (int h = 0; h < 2; ++h) {
-            unsigned* t = c->work.as<unsigned>() + h * c->work_stride + rtk::kDealTable;
-            HIP_TRY(hipMemcpyAsync(t, raster.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemsetAsync(t + n, 0, n * sizeof(unsigned), stream));
-        }
-        HIP_TRY(hipStreamSynchronize(stream));   // (raster is pageable and local)
+        for (int h = 0; h < 2; ++h)
+            HIP_TRY(hipMemsetAsync(c->work.as<unsigned>() + h * c->work_stride + rtk::kDealTable + n, 0, n * sizeof(unsigned), stream));
+        HIP_TRY(upload(raster.data()));
         K.tile_major = rtk::kDealMeasure;
     }
     if (d.build) {
@@ -335,19 +358,25 @@ static int deal_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params* p
         }
         std::vector<uint64_t> costs(n);   // (overlapped batches count on both counters' tables)
         for (size_t i = 0; i < n; ++i) costs[i] = (uint64_t)part[i] + part[n + i];
-        const std::vector<uint32_t>& order = c->deal.finish_build(costs.data());
-        for (int h = 0; h < 2 && e == hipSuccess; ++h)
-            e = hipMemcpyAsync(c->work.as<unsigned>() + h * c->work_stride + rtk::kDealTable, order.data(), n * sizeof(uint32_t),
-                               hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (the pageable copy's source is the cache's, kept; the sync is cheap here)
+        e = upload(c->deal.finish_build(costs.data()).data());   // (a tile the measuring render skipped: cost 0, at the end)
         if (e != hipSuccess) {
             c->deal.fail_build();
+            return hip_fail(e, "deal order: upload");
+        }
+    } else if (d.ordered && c->deal_sky_gen != want_gen) {
+        const hipError_t e = upload(c->deal.order().data());
+        if (e != hipSuccess) {
+            c->deal.drop();
             return hip_fail(e, "deal order: upload");
         }
     }
     if (d.ordered) {
         K.tile_major = rtk::kDealOrdered;
         c->last_deal_n = img_tiles;
+    }
+    if (sky) {
+        *dealt_tiles = img_tiles - c->sky_n;
+        c->stats.sky_tiles = c->sky_n;
     }
     return RT_OK;
 }
@@ -358,6 +387,7 @@ static int deal_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params* p
 // spheres variant's timed staged per-sample pool kernels read it (trace_launch.hpp picks the
 // CfgPrimary instantiation); any other render, or a frame whose table would exceed
 // rtpc::kMaxTableBytes, walks every primary ray. `stream` already waits for the context's earlier work.
+// The table's all-sky tile flags (RT_OPT_SKIP_SKY_TILES) are built, kept and replaced with it.
 static int primary_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, const rtp::Plan& pl, bool count_work,
                          hipStream_t stream, rtk::KParams& K, rtk::LaunchOpts& o)
 {
@@ -376,13 +406,23 @@ static int primary_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params
         c->primary_valid = false;
         int rc = c->primary_tab.reserve(stream, bytes + 16);
         if (rc) return rc;
+        const size_t n_tiles = (size_t)rtpc::tiles_x_of(p->width) * (size_t)rtpc::tiles_y_of(p->height);
+        rc = c->sky_tab.reserve(stream, 16 + n_tiles);
+        if (rc) return rc;
         unsigned* const flagged = reinterpret_cast<unsigned*>(c->primary_tab.as<char>() + bytes);
         HIP_TRY(c->ev_pc.record(0, stream));
         HIP_TRY(rtk::launch_primary_candidates(c->S, *cam, p->width, p->height, c->opt_primary_k, c->primary_tab.p, flagged, stream));
+        // its all-sky tiles (RT_OPT_SKIP_SKY_TILES), whatever the option says now: it may change while the table is kept
+        HIP_TRY(rtk::launch_primary_sky_tiles(c->primary_tab.p, p->width, p->height, c->sky_dev(), c->sky_tab.as<unsigned>(), stream));
         HIP_TRY(c->ev_pc.record(1, stream));
-        unsigned n_flagged = 0;
+        unsigned n_flagged = 0, n_sky = 0;
+        c->sky_flags.assign(n_tiles, 0);
         HIP_TRY(hipMemcpyAsync(&n_flagged, flagged, sizeof n_flagged, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&n_sky, c->sky_tab.p, sizeof n_sky, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(c->sky_flags.data(), c->sky_dev(), n_tiles, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
+        c->sky_n = (int64_t)n_sky;
+        c->sky_gen++;
         float ms = 0.0f;
         HIP_TRY(c->ev_pc.elapsed(0, &ms));
         c->primary_key = key;
@@ -445,6 +485,7 @@ int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_
         for (int i = 0; i < 3; ++i) HIP_TRY(c->ev.record(i, stream));
         write_stats(c, rtp::Plan{}, chunk, 0, false);
         c->last_deal_n = 0;
+        c->stats.sky_tiles = 0;
         return RT_OK;
     }
 
@@ -501,10 +542,23 @@ int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_
     o.count = rq.count_work;
     o.waves_per_simd = &waves_per_simd;
     const rtk::SampleTiles tiles{lay.w, lay.rows, (lay.w + 7) / 8, pl.f32};
-    rc = deal_setup(c, cam, p, pl, sink.moments != nullptr, img_tiles, stream, K);
-    if (rc) return rc;
     rc = primary_setup(c, cam, p, pl, rq.count_work, stream, K, o);
     if (rc) return rc;
+    // RT_OPT_SKIP_SKY_TILES: a direct render with a table, through the per-sample buffer in one batch
+    // (reduce_samples_tiled takes the flags; the carry form and the ring's chunk partials do not, so
+    // those renders trace every tile), at max_depth >= 1 (at 0 every sample is black, not the
+    // background). deal_setup adds its own condition: the render goes through a deal table.
+    const bool sky_ok = c->opt_sky && o.primary && p->max_depth >= 1 && !sink.acc && !sink.moments && pl.per_sample &&
+                        !pl.ring && pl.n_batches == 1 && !open && c->sky_n > 0 && c->sky_n < img_tiles;
+    int64_t dealt_tiles = (int64_t)K.tiles_x * K.tiles_y;
+    c->stats.sky_tiles = 0;
+    rc = deal_setup(c, cam, p, pl, sink.moments != nullptr, img_tiles, sky_ok, stream, K, &dealt_tiles);
+    if (rc) return rc;
+    rtk::SkyTiles sky;
+    if (c->stats.sky_tiles > 0) {
+        sky.flags = c->sky_dev();
+        for (int i = 0; i < 3; ++i) sky.rec[i] = 0.0 + 1.0 * K.bg[i];   // a sample that meets nothing: cr = 0 + T * bg, T = 1
+    }
 
     if (pl.own_total) HIP_TRY(hipMemsetAsync(acc, 0, pl.px_bytes, stream));
     if (rq.count_work) {
@@ -533,7 +587,7 @@ int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_
             const unsigned g = items ? (unsigned)K.block_chunks : (unsigned)K.block_samples;   // (POOL: samples)
             const unsigned n = items ? (unsigned)K.n_chunks : (unsigned)(K.spp - K.sample_begin);
             const unsigned n_groups = (n + g - 1) / std::max(g, 1u);
-            K.n_work_blocks = (unsigned)K.tiles_x * (unsigned)K.tiles_y * n_groups;
+            K.n_work_blocks = (unsigned)dealt_tiles * n_groups;
             K.deal_div = K.tile_major ? n_groups : (unsigned)K.tiles_x * (unsigned)K.tiles_y;
         }
         // batch bi's buffer half, trace stream and work counter (one of each per overlapped batch)
@@ -560,7 +614,7 @@ int run_range(rt_ctx* c, const rt_camera* cam, const rt_render_params* p, int s_
             if (acc) HIP_TRY(rtk::launch_accumulate(buf, acc, n_px, K.n_chunks, stream));
             else HIP_TRY(rtk::launch_reduce(buf, sink.out, sink.f64, n_px, K.n_chunks, sink.scale, stream));
         } else if (!open) {
-            HIP_TRY(rtk::launch_reduce_samples(buf, sink.out, sink.f64, tiles, b1 - b0, chunk, sink.scale, stream));
+            HIP_TRY(rtk::launch_reduce_samples(buf, sink.out, sink.f64, tiles, b1 - b0, chunk, sink.scale, stream, sky));
         } else {
             HIP_TRY(rtk::launch_reduce_samples_carry(buf, acc, open, tiles, b1 - b0, chunk,
                                                      (int)(((long long)b0 - s_begin) % chunk), bi == pl.n_batches - 1,
@@ -914,6 +968,10 @@ int rt_ctx_set_option(rt_ctx* c, int key, int64_t v)
         if (v < 1 || v > rtpc::kSlots) return fail(RT_ERR_INVALID, "primary candidates per pixel out of range (1..7)");
         c->opt_primary_k = (int)v;
         return RT_OK;
+    case RT_OPT_SKIP_SKY_TILES:
+        if (v < 0 || v > 1) return fail(RT_ERR_INVALID, "skip sky tiles out of range (0 off, 1 on)");
+        c->opt_sky = (int)v;
+        return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
 }
@@ -933,6 +991,7 @@ int rt_ctx_get_option(rt_ctx* c, int key, int64_t* v)
     case RT_OPT_AUTO_DEAL_ORDER: *v = c->opt_deal; return RT_OK;
     case RT_OPT_PRIMARY_CANDIDATES: *v = c->opt_primary; return RT_OK;
     case RT_OPT_PRIMARY_CANDIDATES_K: *v = c->opt_primary_k; return RT_OK;
+    case RT_OPT_SKIP_SKY_TILES: *v = c->opt_sky; return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
 }

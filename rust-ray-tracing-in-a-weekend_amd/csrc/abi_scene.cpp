@@ -337,6 +337,20 @@ int rt_primary_candidates_host(const rt_scene_soa* s, const rt_camera* cam, int 
     return RT_OK;
 }
 
+// The all-sky tile flags of that table (primary_candidates.hpp, tile_all_sky): the host twin of what
+// a render builds beside the table when RT_OPT_SKIP_SKY_TILES is on.
+int rt_primary_sky_tiles_host(const rt_scene_soa* s, const rt_camera* cam, int width, int height, int k_max, uint8_t* flags,
+                              int64_t* count)
+{
+    if (!flags || width < 1 || height < 1) return fail(RT_ERR_INVALID, "bad argument");
+    std::vector<rtpc::Record> table((size_t)width * (size_t)height);
+    const int rc = rt_primary_candidates_host(s, cam, width, height, k_max, reinterpret_cast<uint16_t*>(table.data()), nullptr);
+    if (rc) return rc;
+    const int64_t n = rtpc::sky_tiles_host(table.data(), width, height, flags);
+    if (count) *count = n;
+    return RT_OK;
+}
+
 // ---- output ---------------------------------------------------------------------------------
 // write_color (math.rs:119-131) of one f64 channel summed over spp samples: scale = 1.0/spp,
 // sqrt(x * scale), clamp to [0, 0.999] (NaN passes through, math.rs:282-286), 256 * c with

@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "rt/rt_abi.h"
 #include "deal_cache.hpp"
@@ -214,6 +215,14 @@ struct rt_ctx {
     int primary_k = 0;                  //   the k it was built with
     int64_t primary_flagged = 0;        //   its flagged pixels
     EventSpan<2> ev_pc;                 //   around its build
+    // RT_OPT_SKIP_SKY_TILES: the table's all-sky tiles, built, cached and dropped with it
+    int opt_sky = 1;                    // the option (0: every tile is traced)
+    DevBuf sky_tab;                     // one u32 (how many are set), 12 bytes unused, then a flag byte per raster tile
+    std::vector<uint8_t> sky_flags;     //   the host's copy of the flags (the deal tables are filtered with it)
+    int64_t sky_n = 0;                  //   how many are set
+    uint64_t sky_gen = 0;               //   counts the builds (from 1)
+    uint64_t deal_sky_gen = 0;          // the build whose flagged tiles the device's deal tables leave out (0: they list every tile)
+    uint8_t* sky_dev() const { return reinterpret_cast<uint8_t*>(sky_tab.p) + 16; }
 };
 
 // Orders what a call enqueues on `stream` after everything this context enqueued on another

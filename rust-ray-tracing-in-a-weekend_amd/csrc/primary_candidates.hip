@@ -43,4 +43,31 @@ hipError_t launch_primary_candidates(const SceneDev& S, const rt_camera& cam, in
     return hipGetLastError();
 }
 
+// The table's all-sky tiles (primary_candidates.hpp, tile_all_sky: the host twin's rule): one thread
+// per 8x8 raster tile reads its pixels' counts, writes the tile's flag byte and counts the set ones.
+__global__ void __launch_bounds__(256) primary_sky_tiles(const rtpc::Record* __restrict__ table, int width, int height,
+                                                         uint8_t* __restrict__ flags, unsigned* __restrict__ n_sky)
+{
+    const int tx_n = rtpc::tiles_x_of(width);
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x, n = (long long)tx_n * rtpc::tiles_y_of(height);
+    bool sky = false;
+    if (t < n) {
+        sky = rtpc::tile_all_sky(table, width, height, (int)(t % tx_n), (int)(t / tx_n));
+        flags[t] = sky ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(sky);   // one add per wave
+    if (m != 0 && (threadIdx.x & 63u) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(n_sky, (unsigned)__popcll(m));
+}
+
+hipError_t launch_primary_sky_tiles(const void* table, int width, int height, uint8_t* flags, unsigned* n_sky, hipStream_t stream)
+{
+    const long long n = (long long)rtpc::tiles_x_of(width) * rtpc::tiles_y_of(height);
+    if (width <= 0 || height <= 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(n_sky, 0, sizeof(unsigned), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(primary_sky_tiles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       (const rtpc::Record*)table, width, height, flags, n_sky);
+    return hipGetLastError();
+}
+
 }  // namespace rtk

@@ -197,6 +197,23 @@ RT_PC_HD Record build_pixel(const rt_bvh_node* nodes, const rt_prim* leaf_prims,
     }
 }
 
+// ---- all-sky tiles (RT_OPT_SKIP_SKY_TILES) --------------------------------------------------------
+// A pixel listed with n == 0 has no primitive any of its primary rays can meet: at max_depth >= 1
+// every sample of it is 0.0 + 1.0 * background, whatever its draws. An 8x8 raster tile (tx, ty) of
+// the frame whose in-frame pixels are all listed so is never dealt to the trace kernel; the
+// reduction sums that constant in the records' place. A flagged pixel (kWalk) is
+// not sky.
+RT_PC_HD int tiles_x_of(int width) { return (width + 7) / 8; }
+RT_PC_HD int tiles_y_of(int height) { return (height + 7) / 8; }
+RT_PC_HD bool tile_all_sky(const Record* table, int width, int height, int tx, int ty)
+{
+    const int x1 = tx * 8 + 8 < width ? tx * 8 + 8 : width, y1 = ty * 8 + 8 < height ? ty * 8 + 8 : height;
+    for (int y = ty * 8; y < y1; ++y)
+        for (int x = tx * 8; x < x1; ++x)
+            if (table[(size_t)y * (size_t)width + (size_t)x].n != 0) return false;
+    return true;
+}
+
 // ---- the host twin (primary_candidates_host.cpp) ------------------------------------------------
 struct TableStats {
     int64_t pixels = 0, flagged = 0, candidates = 0;   // candidates: summed over the pixels not flagged
@@ -206,5 +223,7 @@ struct TableStats {
 TableStats build_host(const rt_bvh_node* nodes, const rt_prim* leaf_prims, int32_t root, const rt_camera& cam, int width,
                       int height, int k_max, Record* out);
 inline size_t table_bytes(int width, int height) { return (size_t)width * (size_t)height * sizeof(Record); }
+// the all-sky flags of a table, flags[ty * tiles_x_of(width) + tx] = 1 or 0; returns how many are set
+int64_t sky_tiles_host(const Record* table, int width, int height, uint8_t* flags);
 
 }  // namespace rtpc

@@ -26,4 +26,18 @@ TableStats build_host(const rt_bvh_node* nodes, const rt_prim* leaf_prims, int32
     return st;
 }
 
+int64_t sky_tiles_host(const Record* table, int width, int height, uint8_t* flags)
+{
+    int64_t n = 0;
+    const int tx_n = tiles_x_of(width), ty_n = tiles_y_of(height);
+    for (int ty = 0; ty < ty_n; ++ty) {
+        for (int tx = 0; tx < tx_n; ++tx) {
+            const bool sky = tile_all_sky(table, width, height, tx, ty);
+            flags[(size_t)ty * (size_t)tx_n + (size_t)tx] = sky ? 1 : 0;
+            n += sky;
+        }
+    }
+    return n;
+}
+
 }  // namespace rtpc

@@ -34,10 +34,14 @@ constexpr int kReduceWaves = 8;
 template <typename T, typename Rec = double>
 __global__ void __launch_bounds__(64 * kReduceWaves) reduce_samples_tiled(const Rec* __restrict__ samples,
                                                                           T* __restrict__ out, SampleTiles g,
-                                                                          int n_samples, int chunk, double scale)
+                                                                          int n_samples, int chunk, double scale,
+                                                                          SkyTiles sky)
 {
     __shared__ double part[kReduceWaves][3][64];
     const unsigned tile = blockIdx.x;
+    // a tile the trace launch was not dealt (RT_OPT_SKIP_SKY_TILES; block-uniform): its records were
+    // never written, and every one of them would be sky.rec — the same additions below, no loads
+    const bool sky_tile = sky.flags != nullptr && sky.flags[tile] != 0;
     const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
     const Rec* base = samples + ((size_t)tile * (size_t)n_samples * 64 + (size_t)lane) * 3;
     const int n_chunks = (n_samples + chunk - 1) / chunk;
@@ -48,6 +52,13 @@ __global__ void __launch_bounds__(64 * kReduceWaves) reduce_samples_tiled(const 
             const int j0 = c * chunk, j1 = min(n_samples, j0 + chunk);
             double cr = 0.0, cg = 0.0, cb = 0.0;
             int j = j0;
+            if (sky_tile) {
+                for (; j < j1; ++j) {
+                    cr = cr + sky.rec[0];
+                    cg = cg + sky.rec[1];
+                    cb = cb + sky.rec[2];
+                }
+            }
             for (; j + 4 <= j1; j += 4) {
                 Rec v[4][3];
 #pragma unroll
@@ -303,7 +314,7 @@ hipError_t launch_trace(const SceneDev& S, const KParams& Ph, const KParams* P, 
 }
 
 hipError_t launch_reduce_samples(const double* samples, void* out, bool f64, SampleTiles g, int n_samples,
-                                 int chunk, double scale, hipStream_t stream)
+                                 int chunk, double scale, hipStream_t stream, const SkyTiles& sky)
 {
     const long long tiles = (long long)tiled_pixels(g.width, g.n_rows) / 64;   // one block per tile
     const float* rec32 = reinterpret_cast<const float*>(samples);
@@ -311,16 +322,16 @@ hipError_t launch_reduce_samples(const double* samples, void* out, bool f64, Sam
     const dim3 grid((unsigned)tiles), block(64 * kReduceWaves);
     if (g.f32_records && f64)
         hipLaunchKernelGGL((reduce_samples_tiled<double, float>), grid, block, 0, stream, rec32, (double*)out, g,
-                           n_samples, chunk, scale);
+                           n_samples, chunk, scale, sky);
     else if (g.f32_records)
         hipLaunchKernelGGL((reduce_samples_tiled<float, float>), grid, block, 0, stream, rec32, (float*)out, g,
-                           n_samples, chunk, scale);
+                           n_samples, chunk, scale, sky);
     else if (f64)
         hipLaunchKernelGGL(reduce_samples_tiled<double>, grid, block, 0, stream, samples, (double*)out, g, n_samples,
-                           chunk, scale);
+                           chunk, scale, sky);
     else
         hipLaunchKernelGGL(reduce_samples_tiled<float>, grid, block, 0, stream, samples, (float*)out, g, n_samples,
-                           chunk, scale);
+                           chunk, scale, sky);
     return hipGetLastError();
 }
 

@@ -192,10 +192,20 @@ hipError_t launch_trace(const SceneDev& S, const KParams& Ph, const KParams* P, 
 // table = width x height 16-byte records, *flagged = the pixels flagged "walk"
 hipError_t launch_primary_candidates(const SceneDev& S, const rt_camera& cam, int width, int height, int k_max, void* table,
                                      unsigned* flagged, hipStream_t stream);
+// and the table's all-sky 8x8 raster tiles (RT_OPT_SKIP_SKY_TILES): flags = one byte per tile, *n_sky = how many are set
+hipError_t launch_primary_sky_tiles(const void* table, int width, int height, uint8_t* flags, unsigned* n_sky,
+                                    hipStream_t stream);
+// RT_OPT_SKIP_SKY_TILES: the raster tiles the trace launch was not dealt (flags[tile] != 0; null:
+// none) and what every sample record of theirs would hold (0.0 + 1.0 * background, per channel)
+struct SkyTiles {
+    const uint8_t* flags = nullptr;
+    double rec[3] = {0.0, 0.0, 0.0};
+};
 // pool schedule: per pixel, chunk sums of its samples (sample order) added to 0.0, scaled to out
-// (out and the carried sums are in pixel order k * width + x)
+// (out and the carried sums are in pixel order k * width + x); a tile flagged in `sky` sums
+// sky.rec in place of every record, addition for addition
 hipError_t launch_reduce_samples(const double* samples, void* out, bool f64, SampleTiles g, int n_samples,
-                                 int chunk, double scale, hipStream_t stream);
+                                 int chunk, double scale, hipStream_t stream, const SkyTiles& sky = SkyTiles{});
 // the same across buffer batches: acc = closed chunks' total, open = the chunk in progress
 // (pos of its samples seen before this batch); close ends the last chunk
 hipError_t launch_reduce_samples_carry(const double* samples, double* acc, double* open, SampleTiles g,

@@ -54,6 +54,7 @@ RT_OPT_COMM_DIRECT = 10
 RT_OPT_AUTO_DEAL_ORDER = 11   # 1 (default): whole frames dealt in self-measured cost order; 0 off; 2 measure only
 RT_OPT_PRIMARY_CANDIDATES = 12    # 1 (default): new samples take their first hit from their pixel's candidate list; 0 off
 RT_OPT_PRIMARY_CANDIDATES_K = 13  # candidates per pixel before it is flagged "walk" (1..7, default 7; tests force 1)
+RT_OPT_SKIP_SKY_TILES = 14        # 1 (default): 8x8 tiles whose pixels' candidate lists are all empty are not traced; 0 off
 # SAH builder options (rt_world_set_build_option)
 RT_BUILD_C_ISECT = 1
 RT_BUILD_MAX_LEAF = 2
@@ -92,7 +93,7 @@ EXPORTED = [
     "rt_adaptive_state_create", "rt_adaptive_state_destroy", "rt_adaptive_state_advance",
     "rt_adaptive_state_resolve", "rt_adaptive_state_get", "rt_adaptive_state_set",
     "rt_adaptive_state_last_stats", "rt_adaptive_next_group_host",
-    "rt_primary_candidates_host",
+    "rt_primary_candidates_host", "rt_primary_sky_tiles_host",
     "rt_trace_rays", "rt_query_last_stats", "rt_camera_rays",
 ]
 
@@ -166,7 +167,7 @@ class Stats(ctypes.Structure):
                 ("trace_buf_bytes", ctypes.c_int64), ("overlapped", ctypes.c_int32), ("reserved0", ctypes.c_int32),
                 ("ring_bytes", ctypes.c_int64),
                 ("primary_table_bytes", ctypes.c_int64), ("primary_build_ms", ctypes.c_double),
-                ("primary_walk_share", ctypes.c_double)]
+                ("primary_walk_share", ctypes.c_double), ("sky_tiles", ctypes.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -466,6 +467,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "rt_cost_tile_order": ([P, ctypes.c_int64, P], I),
         "rt_primary_candidates_host": ([ctypes.POINTER(SceneSoA), ctypes.POINTER(Camera), I, I, I, P,
                                         ctypes.POINTER(PrimaryCandidatesInfo)], I),
+        "rt_primary_sky_tiles_host": ([ctypes.POINTER(SceneSoA), ctypes.POINTER(Camera), I, I, I, P,
+                                       ctypes.POINTER(ctypes.c_int64)], I),
         "rt_render_adaptive": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
                                 ctypes.POINTER(AdaptiveParams), ctypes.POINTER(AdaptiveOut)], I),
         "rt_render_adaptive_halves": ([P, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams),
@@ -653,6 +656,16 @@ def primary_candidates_host(soa: SceneSoA, cam: Camera, width: int, height: int,
     _check(load_library().rt_primary_candidates_host(ctypes.byref(soa), ctypes.byref(cam), width, height, k_max,
                                                      rec.ctypes.data, ctypes.byref(info)), "rt_primary_candidates_host")
     return rec, info
+
+
+def primary_sky_tiles_host(soa: SceneSoA, cam: Camera, width: int, height: int, k_max: int = 7):
+    """rt_primary_sky_tiles_host: (flags (ceil(height / 8), ceil(width / 8)) uint8 — 1 where every pixel of
+    the 8x8 raster tile within the frame has an empty candidate list — and how many are 1)."""
+    flags = np.zeros(((height + 7) // 8, (width + 7) // 8), dtype=np.uint8)
+    n = ctypes.c_int64()
+    _check(load_library().rt_primary_sky_tiles_host(ctypes.byref(soa), ctypes.byref(cam), width, height, k_max,
+                                                    flags.ctypes.data, ctypes.byref(n)), "rt_primary_sky_tiles_host")
+    return flags, n.value
 
 
 def camera_rays(cam: Camera, width: int, height: int, seed: int, sample: int, tiled: bool = False) -> np.ndarray:
