@@ -300,6 +300,9 @@ typedef struct rt_stats {
     /* RT_OPT_SKIP_SKY_TILES (additive to ABI v6) */
     int64_t sky_tiles;           /* 8x8 tiles the last render did not trace: every pixel of them sees only the
                                     background (0: the option off, or a render it does not apply to) */
+    /* RT_OPT_DEFER_ROOTS (additive to ABI v6) */
+    int64_t defer_roots;         /* 1: the last render's trace kernel was the primary-candidate kernel with deferred
+                                    sphere roots; 0: any other kernel (the option off, or no primary-candidate table) */
 } rt_stats;
 int rt_last_stats(rt_ctx* ctx, rt_stats* out);
 
@@ -1259,7 +1262,13 @@ int rt_ctx_set_variant(rt_ctx* ctx, int slab32, int lds_stack, int lds_nodes);
  *                           at max_depth >= 1, traces no 8x8 tile whose pixels' candidate lists are all
  *                           empty: each of their samples is exactly the background, and the reduction
  *                           sums that constant as it would have summed the records (rt_stats.sky_tiles).
- *                           0: every tile is traced. Same bits either way. */
+ *                           0: every tile is traced. Same bits either way.
+ *   RT_OPT_DEFER_ROOTS      1 (default): where the primary-candidate kernel runs (RT_OPT_PRIMARY_CANDIDATES), its
+ *                           sphere tests decide "near or far root, in range, closer than the best" from f32
+ *                           brackets of the roots with a proven bound, fall back to the exact root where a
+ *                           bracket cannot decide, and compute the exact f64 root of a cast's closest sphere
+ *                           only (rt_stats.defer_roots); 0: every candidate's exact root, as before. Same bits
+ *                           either way. */
 enum {
     RT_OPT_TRACE_BUF_BYTES = 1,
     RT_OPT_BATCH_OVERLAP = 2,
@@ -1273,7 +1282,8 @@ enum {
     RT_OPT_AUTO_DEAL_ORDER = 11,
     RT_OPT_PRIMARY_CANDIDATES = 12,
     RT_OPT_PRIMARY_CANDIDATES_K = 13,
-    RT_OPT_SKIP_SKY_TILES = 14
+    RT_OPT_SKIP_SKY_TILES = 14,
+    RT_OPT_DEFER_ROOTS = 15
 };
 int rt_ctx_set_option(rt_ctx* ctx, int key, int64_t value);
 int rt_ctx_get_option(rt_ctx* ctx, int key, int64_t* value);

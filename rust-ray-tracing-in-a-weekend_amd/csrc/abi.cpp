@@ -395,6 +395,7 @@ static int primary_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params
     st.primary_table_bytes = 0;
     st.primary_build_ms = 0.0;
     st.primary_walk_share = 0.0;
+    st.defer_roots = 0;
     const size_t bytes = rtpc::table_bytes(p->width, p->height);
     if (!c->opt_primary || pl.variant != rtk::FEAT_SET_SPHERES || pl.f32 || pl.schedule != RT_SCHED_POOL || !pl.shape.s16 ||
         pl.seed_stage_bytes == 0 || count_work || bytes > rtpc::kMaxTableBytes || p->width < 2 || p->height < 2)
@@ -433,6 +434,8 @@ static int primary_setup(rt_ctx* c, const rt_camera* cam, const rt_render_params
     }
     K.primary = c->primary_tab.as<uint4>();
     o.primary = 1;
+    o.defer_roots = c->opt_defer_roots;   // the CfgDefer kernel, which exists wherever the primary-candidate one does
+    st.defer_roots = c->opt_defer_roots;
     st.primary_table_bytes = (int64_t)bytes;
     st.primary_walk_share = (double)c->primary_flagged / ((double)p->width * (double)p->height);
     return RT_OK;
@@ -972,6 +975,10 @@ int rt_ctx_set_option(rt_ctx* c, int key, int64_t v)
         if (v < 0 || v > 1) return fail(RT_ERR_INVALID, "skip sky tiles out of range (0 off, 1 on)");
         c->opt_sky = (int)v;
         return RT_OK;
+    case RT_OPT_DEFER_ROOTS:
+        if (v < 0 || v > 1) return fail(RT_ERR_INVALID, "defer roots out of range (0 off, 1 on)");
+        c->opt_defer_roots = (int)v;
+        return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
 }
@@ -992,6 +999,7 @@ int rt_ctx_get_option(rt_ctx* c, int key, int64_t* v)
     case RT_OPT_PRIMARY_CANDIDATES: *v = c->opt_primary; return RT_OK;
     case RT_OPT_PRIMARY_CANDIDATES_K: *v = c->opt_primary_k; return RT_OK;
     case RT_OPT_SKIP_SKY_TILES: *v = c->opt_sky; return RT_OK;
+    case RT_OPT_DEFER_ROOTS: *v = c->opt_defer_roots; return RT_OK;
     default: return fail(RT_ERR_INVALID, "unknown option");
     }
 }

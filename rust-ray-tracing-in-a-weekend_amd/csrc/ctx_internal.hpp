@@ -217,6 +217,7 @@ struct rt_ctx {
     EventSpan<2> ev_pc;                 //   around its build
     // RT_OPT_SKIP_SKY_TILES: the table's all-sky tiles, built, cached and dropped with it
     int opt_sky = 1;                    // the option (0: every tile is traced)
+    int opt_defer_roots = 1;            // RT_OPT_DEFER_ROOTS (0: the primary-candidate kernel computes every candidate's exact root)
     DevBuf sky_tab;                     // one u32 (how many are set), 12 bytes unused, then a flag byte per raster tile
     std::vector<uint8_t> sky_flags;     //   the host's copy of the flags (the deal tables are filtered with it)
     int64_t sky_n = 0;                  //   how many are set

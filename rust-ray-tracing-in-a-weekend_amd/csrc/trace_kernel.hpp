@@ -120,6 +120,7 @@ struct LaunchOpts {
     int pool;           // RT_SCHED_*: 0 chunks, 1 per-sample pool (per-sample output), 2 item pool (partials)
     int f32;            // the f32 fast mode (RT_PREC_F32)
     int primary = 0;    // KParams.primary is set: the per-sample pool's primary-candidate kernel, where one exists
+    int defer_roots = 0;  // RT_OPT_DEFER_ROOTS: with `primary`, the kernel whose sphere tests defer the exact root (CfgDefer)
     int* waves_per_simd = nullptr;  // out (optional): resident waves per SIMD of the launched trace kernel
 };
 

@@ -33,6 +33,11 @@ hipError_t launch_variant(const Launch& L, const LaunchOpts& o, hipStream_t stre
                     if constexpr (RT_STAGE_SEEDS != 0 && C::SHAPE.s16 && F == FEAT_SET_SPHERES && !COUNT)
                         return any_static_lds({(const void*)trace_pool<CfgPrimary<C>, false>, (const void*)trace_pool<CfgPrimary<C>, false, true>});
                     else return false;
+                }() ||
+                [] {   // and those with deferred sphere roots
+                    if constexpr (RT_STAGE_SEEDS != 0 && C::SHAPE.s16 && F == FEAT_SET_SPHERES && !COUNT)
+                        return any_static_lds({(const void*)trace_pool<CfgDefer<C>, false>, (const void*)trace_pool<CfgDefer<C>, false, true>});
+                    else return false;
                 }();
             if (static_lds) k = without_stack16(k);
         }
@@ -53,6 +58,8 @@ hipError_t launch_variant(const Launch& L, const LaunchOpts& o, hipStream_t stre
                 hipLaunchKernelGGL(kernel, dim3(nb), dim3(bt), lds, stream, S, L.P, L.out, L.counters, L.work);
             };
             if constexpr (RT_STAGE_SEEDS != 0 && C1::SHAPE.s16 && !F32 && F == FEAT_SET_SPHERES && !COUNT) {
+                if (seed_bytes && L.primary && L.defer_roots)
+                    return go(L.max_waves ? trace_pool<CfgDefer<C1>, false, true> : trace_pool<CfgDefer<C1>, false>);
                 if (seed_bytes && L.primary)
                     return go(L.max_waves ? trace_pool<CfgPrimary<C1>, false, true> : trace_pool<CfgPrimary<C1>, false>);
             }

@@ -20,6 +20,7 @@ struct Launch {
     int* waves_per_simd;           // out (optional): resident blocks per CU = waves per SIMD (4-wave blocks)
     unsigned max_waves = 0;        // per-sample pool with the in-kernel reduction: waves its ring holds
     bool primary = false;          // KParams.primary is set (LaunchOpts.primary)
+    bool defer_roots = false;      // with it: the CfgDefer kernels (LaunchOpts.defer_roots)
 };
 
 // Resident blocks per CU of a kernel (registers, LDS); waves per SIMD reported to the caller.

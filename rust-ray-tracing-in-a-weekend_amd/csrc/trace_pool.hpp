@@ -195,6 +195,7 @@ __device__ __forceinline__ void generate_primary(const SceneDev& S, const KParam
             best.sub = 0;
             best.side = 0;
             best.prim = -1;
+            [[maybe_unused]] rtrb::Best bb = rtrb::none();   // CfgDefer: the slot and an f32 bracket of its t (root_bracket.hpp)
             // the record's slots (halfwords 1..7) in order: three from the first pair of words, then four
             uint64_t a = ((uint64_t)rec.y << 32 | (uint64_t)rec.x) >> 16;
             const uint64_t b = (uint64_t)rec.w << 32 | (uint64_t)rec.z;
@@ -203,7 +204,9 @@ __device__ __forceinline__ void generate_primary(const SceneDev& S, const KParam
             for (unsigned i = 0; __ballot(i + 1 < n_cand) != 0; ++i) {
                 if (i + 1 < n_cand) {
                     const int slot = (int)((unsigned)a & 0xffffu);
-                    if (simple_t<C>(S.leaf_prims[slot], r, t_min, t_max, best.t, best.side, cnt, false)) {
+                    if constexpr (C::DEFER) {
+                        (void)sphere_defer_t<C>(S, r, rtrb::ya32(r.ya), slot, t_min, bb);
+                    } else if (simple_t<C>(S.leaf_prims[slot], r, t_min, t_max, best.t, best.side, cnt, false)) {
                         best.prim = slot;
                         t_max = best.t;
                     }
@@ -211,12 +214,14 @@ __device__ __forceinline__ void generate_primary(const SceneDev& S, const KParam
                 a >>= 16;
                 if (i == 2) a = b;
             }
+            if constexpr (C::DEFER) best.prim = bb.prim;
             if (n_cand != 0) {
                 if (best.prim < 0) {   // main.rs:37: background; the sample ends
                     cr = cr + Tr * P.bg[0];
                     cg = cg + Tg * P.bg[1];
                     cb = cb + Tb * P.bg[2];
                 } else {
+                    if constexpr (C::DEFER) (void)sphere_exact_of<C>(S, r, best.prim, t_min, best.t);   // the winner's exact root, once
                     finish_hit<C>(S, r, best, h);
                     pending = shade_begin<C>(S, h, Tr, Tg, Tb, cr, cg, cb);
                 }

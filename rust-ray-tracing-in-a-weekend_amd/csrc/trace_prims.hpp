@@ -30,6 +30,29 @@ __device__ __forceinline__ bool sphere_t(double cx, double cy, double cz, double
     return true;
 }
 
+// sphere_t in two parts (CfgDefer, root_bracket.hpp): the quadratic's half_b and discriminant, in
+// sphere_t's own expressions, and the root in [t_min, +inf) from them — the root sphere_t accepts
+// a sphere with whatever its t_max (the near root if that is >= t_min, else the far one).
+__device__ __forceinline__ void sphere_quad(double cx, double cy, double cz, double radius, const RayT<double>& r,
+                                            double& half_b, double& disc)
+{
+    const double ocx = r.ox - cx, ocy = r.oy - cy, ocz = r.oz - cz;
+    half_b = ocx * r.dx + ocy * r.dy + ocz * r.dz;
+    const double c = (ocx * ocx + ocy * ocy + ocz * ocz) - radius * radius;
+    disc = half_b * half_b - r.a * c;
+}
+__device__ __forceinline__ bool sphere_root(double half_b, double disc, const RayT<double>& r, double t_min, double& t)
+{
+    const double sqrtd = __builtin_sqrt(disc);
+    double root = div_rcp(-half_b - sqrtd, r.a, r.ya);
+    if (root < t_min) {
+        root = div_rcp(-half_b + sqrtd, r.a, r.ya);
+        if (root < t_min) return false;
+    }
+    t = root;
+    return true;
+}
+
 // A sphere-bounded ConstantMedium's two boundary queries (hittable.rs:430-434: hit over
 // (-inf, inf), then over (t1 + 0.0001, inf)) from one quadratic: both calls of sphere_t above
 // compute the same discriminant and roots, and differ only in the range the roots are checked

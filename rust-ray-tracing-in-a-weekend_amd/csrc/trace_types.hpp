@@ -138,6 +138,7 @@ struct Cfg {
     using Real = typename std::conditional<F32_, float, double>::type;
     static constexpr bool STAGE = false;   // (CfgStage below)
     static constexpr bool PRIMARY = false; // (CfgPrimary below)
+    static constexpr bool DEFER = false;   // (CfgDefer below)
 };
 // The configuration of trace_pool's staged instantiations (launch_shapes.hpp, RT_STAGE_SEEDS): the
 // wave seeds and jitters a whole row of samples at once. A configuration of its own rather than a
@@ -153,6 +154,14 @@ struct CfgStage : C {
 template <class C>
 struct CfgPrimary : CfgStage<C> {
     static constexpr bool PRIMARY = true;
+};
+
+// The primary-candidate kernel whose sphere tests decide from f32 brackets of the roots and compute
+// the exact root of a cast's winner only (root_bracket.hpp, RT_OPT_DEFER_ROOTS; trace_walk.hpp,
+// trace_world_defer). A wrapper once more: the CfgPrimary kernels keep their symbols and their code.
+template <class C>
+struct CfgDefer : CfgPrimary<C> {
+    static constexpr bool DEFER = true;
 };
 
 // The configuration of code reached only through an instance or a medium boundary: the

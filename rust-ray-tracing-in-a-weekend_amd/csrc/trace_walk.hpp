@@ -2,6 +2,7 @@
 // LDS or L1/L2 and the block's LDS layout, traverse, Translate / RotateY instances, constant media,
 // the hit record of the closest hit (finish_hit) and trace_world, one cast of a world-space ray.
 #pragma once
+#include "root_bracket.hpp"
 #include "trace_prims.hpp"
 
 namespace rtk {
@@ -94,10 +95,15 @@ __device__ __forceinline__ LdsLayout lds_layout_of(const SceneDev& S)
 // Closest hit in a BVH (nodes + leaf ranges of slots j, whose records are leaf_prims[j]).
 // `leaf(slot, t_max, best)` tests one primitive; on a closer hit it fills best (t and sub
 // ids) and returns true; best.prim is then the slot.
-template <class C, bool NL = false, class LeafFn, class R = typename C::Real>
+// CfgDefer's top-level walk (DEFER): best is an rtrb::Best, the slot and an f32 bracket of its
+// exact t, which `leaf(slot, best)` updates itself; the walk carries no f64 t_max, and prunes by the
+// bracket's upper end (conservative, and strictly above the exact t: a tie is never pruned).
+template <class C, bool NL = false, class LeafFn, class R = typename C::Real, class Best = HitRefT<R>>
 __device__ __forceinline__ bool traverse(const SceneDev& S, int root, const RayT<R>& r, R t_min, R t_max,
-                                         HitRefT<R>& best, StackT<C>& stack, int sp0, Count& cnt, LeafFn&& leaf)
+                                         Best& best, StackT<C>& stack, int sp0, Count& cnt, LeafFn&& leaf)
 {
+    constexpr bool DEFER = C::DEFER && NL && std::is_same<Best, rtrb::Best>::value;
+    static_assert(!DEFER || C::S32, "deferred roots: the f32-slab kernels");
     // NL: this is the TLAS, whose first S.n_lds_nodes nodes (BFS order) were copied into
     // LDS at block start; deeper nodes are read from L1/L2
     const rt_bvh_node* lds_nodes =
@@ -121,6 +127,7 @@ __device__ __forceinline__ bool traverse(const SceneDev& S, int root, const RayT
         tmin_f = f32_down(t_min);
         tmax_f = f32_up(t_max);
     }
+    if constexpr (DEFER) tmax_f = best.hi;   // (the pre-leaf's hit, or +inf)
     // TLAS entirely in LDS, f32 slabs (OctNodes): the node is the 80-B LdsNode layout and
     // node references are byte offsets; per axis one 16-B read at the offset the ray's
     // direction sign selects gives both children's near planes, then their far planes, so
@@ -211,7 +218,9 @@ __device__ __forceinline__ bool traverse(const SceneDev& S, int root, const RayT
         for (int i = 0; i < count; ++i) {
             if (C::COUNT && first_active_lane()) cnt.wave_leaves++;
             const int slot = first + i;
-            if (leaf(slot, t_max, best)) {
+            if constexpr (DEFER) {
+                if (leaf(slot, best)) tmax_f = best.hi;
+            } else if (leaf(slot, t_max, best)) {
                 best.prim = slot;
                 t_max = best.t;
                 any = true;
@@ -232,6 +241,7 @@ __device__ __forceinline__ bool traverse(const SceneDev& S, int root, const RayT
         cur = pop();
         if (NL) RT_STAMP(cnt.t_leaves, t0);
     }
+    if constexpr (DEFER) return best.prim >= 0;
     return any;
 }
 
@@ -480,12 +490,86 @@ constexpr bool DeferInst() { return RT_DEFER_INST && (C::F & FEAT_INST_BLAS) != 
 template <class C>
 constexpr bool UniformLeaf() { return (C::F & FEAT_INST_BLAS) == 0 && !PreLeaf<C>(); }
 
+// CfgDefer (root_bracket.hpp): the exact root of leaf slot `slot`'s sphere over [t_min, +inf), in
+// sphere_t's arithmetic, and the deferred test of one candidate against the best so far.
+template <class C>
+__device__ __forceinline__ bool sphere_exact_of(const SceneDev& S, const RayT<double>& r, int slot, double t_min, double& t)
+{
+    static_assert((C::F & FEAT_RECT) == 0 && !C::F32, "deferred roots: the f64 spheres variant");
+    const rt_prim& p = S.leaf_prims[slot];
+    double cx, cy, cz, half_b, disc;
+    sphere_center(p, r, (C::F & FEAT_SHUTTER) != 0, cx, cy, cz, (C::F & FEAT_STATIC) != 0);
+    sphere_quad(cx, cy, cz, p.p[3], r, half_b, disc);
+    if (disc < 0.0) return false;
+    return sphere_root(half_b, disc, r, t_min, t);
+}
+template <class C>
+__device__ __forceinline__ bool sphere_defer_t(const SceneDev& S, const RayT<double>& r, float yaf, int slot, double t_min,
+                                               rtrb::Best& best)
+{
+    static_assert((C::F & FEAT_RECT) == 0 && !C::F32, "deferred roots: the f64 spheres variant");
+    const rt_prim& p = S.leaf_prims[slot];
+    double cx, cy, cz, half_b, disc;
+    sphere_center(p, r, (C::F & FEAT_SHUTTER) != 0, cx, cy, cz, (C::F & FEAT_STATIC) != 0);
+    sphere_quad(cx, cy, cz, p.p[3], r, half_b, disc);
+    if (disc < 0.0) return false;   // the sign of disc stays exact
+    return rtrb::closer(
+        best, slot, half_b, disc, yaf, rtrb::down(t_min), rtrb::up(t_min),
+        [&](double& t) { return sphere_root(half_b, disc, r, t_min, t); },
+        [&](int s, double& t) { return sphere_exact_of<C>(S, r, s, t_min, t); });
+}
+
+// trace_world of the CfgDefer kernels: the pre-leaf (the ground sphere, one converged test per
+// cast) stays exact and seeds the bracket; the walk's leaf tests decide from brackets; the winner's
+// exact root — today's bits: the root a sphere is accepted with does not depend on t_max — is
+// computed once, by every hit lane together, before the hit record.
+template <class C>
+__device__ __forceinline__ bool trace_world_defer(const SceneDev& S, const RayT<double>& r, HitT<double>& h, StackT<C>& stack,
+                                                  Count& cnt)
+{
+    static_assert(PreLeaf<C>() && C::S32 && !C::COUNT, "deferred roots: the f64 spheres variant's timed kernels");
+    const double t_min = 0.001;
+    rtrb::Best best = rtrb::none();
+    const float yaf = rtrb::ya32(r.ya);   // the ray's part of every bracket
+    int root = S.tlas_root;
+    if (S.pre_leaf != 0) {   // (wave-uniform)
+        root = S.pre_root;
+        float tn;
+        if (slab32(S.pre_lo, S.pre_hi, r, f32_down(t_min), f32_up(RT_INF), tn)) {
+            const int code = ~S.pre_leaf;
+            double t_max = RT_INF;
+            for (int slot = code >> 5, end = (code >> 5) + (code & 31); slot < end; ++slot) {
+                double t;
+                if (sphere_exact_of<C>(S, r, slot, t_min, t) && !(t_max < t)) {
+                    best.prim = slot;
+                    t_max = t;
+                }
+            }
+            if (best.prim >= 0) {
+                best.lo = f32_down(t_max);
+                best.hi = f32_up(t_max);
+            }
+        }
+    }
+    if (!traverse<C, true>(S, root, r, t_min, RT_INF, best, stack, 0, cnt,
+                           [&](int slot, rtrb::Best& b) { return sphere_defer_t<C>(S, r, yaf, slot, t_min, b); }))
+        return false;
+    HitRefT<double> ref;
+    ref.prim = best.prim;
+    ref.sub = 0;
+    ref.side = 0;
+    (void)sphere_exact_of<C>(S, r, best.prim, t_min, ref.t);
+    finish_hit<C>(S, r, ref, h);
+    return true;
+}
+
 // hit_hittables(world, ray, 0.001, inf) (hittable.rs:43-55) over the TLAS, then the HitRecord of
 // the closest primitive.
 template <class C, class R = typename C::Real>
 __device__ bool trace_world(const SceneDev& S, const RayT<R>& r, HitT<R>& h, StackT<C>& stack, const Keyed& key,
                             Count& cnt)
 {
+    if constexpr (C::DEFER) return trace_world_defer<C>(S, r, h, stack, cnt);
     const R t_min = (R)0.001;
     HitRefT<R> best;
     best.sub = 0;

@@ -55,6 +55,7 @@ RT_OPT_AUTO_DEAL_ORDER = 11   # 1 (default): whole frames dealt in self-measured
 RT_OPT_PRIMARY_CANDIDATES = 12    # 1 (default): new samples take their first hit from their pixel's candidate list; 0 off
 RT_OPT_PRIMARY_CANDIDATES_K = 13  # candidates per pixel before it is flagged "walk" (1..7, default 7; tests force 1)
 RT_OPT_SKIP_SKY_TILES = 14        # 1 (default): 8x8 tiles whose pixels' candidate lists are all empty are not traced; 0 off
+RT_OPT_DEFER_ROOTS = 15           # 1 (default): the primary-candidate kernel computes a cast's winning sphere's exact root only; 0 off
 # SAH builder options (rt_world_set_build_option)
 RT_BUILD_C_ISECT = 1
 RT_BUILD_MAX_LEAF = 2
@@ -167,7 +168,8 @@ class Stats(ctypes.Structure):
                 ("trace_buf_bytes", ctypes.c_int64), ("overlapped", ctypes.c_int32), ("reserved0", ctypes.c_int32),
                 ("ring_bytes", ctypes.c_int64),
                 ("primary_table_bytes", ctypes.c_int64), ("primary_build_ms", ctypes.c_double),
-                ("primary_walk_share", ctypes.c_double), ("sky_tiles", ctypes.c_int64)]
+                ("primary_walk_share", ctypes.c_double), ("sky_tiles", ctypes.c_int64),
+                ("defer_roots", ctypes.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

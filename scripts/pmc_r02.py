@@ -168,8 +168,9 @@ def bench(d, tag, workload, note=""):
 
     def sel(name):
         # (the per-sample pool's staged instantiation is trace_pool<rtk::CfgStage<rtk::Cfg<...> >, ...>, its
-        # primary-candidate form trace_pool<rtk::CfgPrimary<rtk::Cfg<...> >, ...>)
-        m = re.search(r"(trace_pool|trace_chunks)<(?:rtk::Cfg(?:Stage|Primary)<)?rtk::Cfg<(\d+)u, (\w+), (\w+), (\w+), (\w+)(?:, (\w+))?>", name)
+        # primary-candidate form trace_pool<rtk::CfgPrimary<rtk::Cfg<...> >, ...>, that with deferred sphere roots
+        # trace_pool<rtk::CfgDefer<rtk::Cfg<...> >, ...>)
+        m = re.search(r"(trace_pool|trace_chunks)<(?:rtk::Cfg(?:Stage|Primary|Defer)<)?rtk::Cfg<(\d+)u, (\w+), (\w+), (\w+), (\w+)(?:, (\w+))?>", name)
         if not m or m.group(6) == "true":      # skip the count_work variant
             return None
         return m.group(1)
