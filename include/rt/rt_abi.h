@@ -811,7 +811,8 @@ int rt_denoise_last_stats(rt_ctx* ctx, rt_denoise_stats* out);
  *           p->background
  *   normal  the hit record's world-space normal as the material sees it: against the ray
  *           (set_face_normal), mapped back through translate / rotate_y as the reference maps it;
- *           a constant medium's hit keeps the record's normal; a miss (0, 0, 0)
+ *           a constant medium's hit keeps the record's normal ((1, 0, 0) top-level, rotated and turned
+ *           against the ray under an instance: rt_trace_rays, below); a miss (0, 0, 0)
  *   depth   sqrt((ex ex + ey ey) + ez ez), e = the hit point - the ray's origin; a miss 0
  * Sums. Every channel is sum * (1 / p->spp), the sum associated as rt_render's: chunk sums from
  * 0.0 in sample order, added in chunk order to 0.0; the chunk is p->spp_chunk, or rt_render's
@@ -1108,12 +1109,25 @@ int rt_pyramid_last_stats(rt_ctx* ctx, rt_pyramid_stats* out);
  * the one draw of a cast, a constant medium's, is keyed by (seed, key_pixel, key_sample, bounce): the
  * bits of a ray's result depend on that ray and the scene alone — not on the launch, the order of
  * the rays in the array, the batches a call is taken in, the acceleration structure or the kernel
- * variant.
+ * variant. Where two top-level primitives accept exactly the same t (coincident faces: the final
+ * scene's ground boxes tile a grid and share their sides; a test rejects t > t_max only), the record
+ * is that of the one later in rt_scene_soa.prims, which is the later entry of the world's list and
+ * the one hit_hittables' loop keeps, under every acceleration structure. (rt_render's and
+ * rt_render_features' casts keep the record of the later test instead, so under RT_ACCEL_SAH they
+ * may shade the other of two such primitives; t and p are the same. Two primitives of one
+ * instance's BVH with the same t: inner is either, as for a medium bounded by a BVH, below.)
  *   t       in units of d (d is not normalised, as the reference's); +inf: a miss
  *   p, n    the record's point and normal: n against the ray (set_face_normal), both mapped back
- *           through translate / rotate_y as the reference maps them; a medium's hit keeps the
- *           record's (1, 0, 0); a miss: zeros
- *   prim    index in rt_scene_soa.prims of the top-level primitive; -1 on a miss
+ *           through translate / rotate_y as the reference maps them, every level applying
+ *           set_face_normal again (hittable.rs:232-244, 386-415: a hit from inside an instanced box
+ *           is front-facing). A top-level medium's hit keeps the record's (1, 0, 0) and front_face;
+ *           a medium under an instance gets that normal rotated and turned against the ray like
+ *           any other: +-(cos a, 0, -sin a) under translate(rotate_y(., a)), the sign from d.
+ *           A miss: zeros
+ *   prim    index in rt_scene_soa.prims of the top-level primitive; -1 on a miss. Top-level as the
+ *           tables have it: an entry of the world's list is one record, except an rt_world_bvh
+ *           pushed as it is and an instance over a BVH that holds more than plain primitives, whose
+ *           members are top-level records of their own (the instance's ops pushed down to each)
  *   inner   the geometric primitive behind t: prim itself, the child or BLAS primitive of an
  *           instance, the boundary of a medium (through the boundary's instance, if it has one; a
  *           boundary that is a BVH is a set, and inner is then one primitive of it — which one

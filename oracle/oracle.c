@@ -680,8 +680,9 @@ static const Hittable* new_bvh_node(World* w, const Hittable* const* list, int s
 
 static int hittable_hit(const Hittable* h, const Ray* r, double t_min, double t_max, HitRecord* rec);
 
-static int hit_list(const Hittable* const* list, int n, const Ray* r, double t_min, double t_max,
-                    HitRecord* rec)                                                       /* hittable.rs:43-55 */
+/* hittable.rs:43-55; *winner (may be NULL) receives the list index of the record returned */
+static int hit_list_winner(const Hittable* const* list, int n, const Ray* r, double t_min, double t_max,
+                           HitRecord* rec, int* winner)
 {
     double closest_so_far = t_max;
     int any = 0;
@@ -691,9 +692,14 @@ static int hit_list(const Hittable* const* list, int n, const Ray* r, double t_m
             closest_so_far = tmp.t;
             *rec = tmp;
             any = 1;
+            if (winner) *winner = i;
         }
     }
     return any;
+}
+static int hit_list(const Hittable* const* list, int n, const Ray* r, double t_min, double t_max, HitRecord* rec)
+{
+    return hit_list_winner(list, n, r, t_min, t_max, rec, NULL);
 }
 
 static int sphere_hit(V3 center, double radius, const Ray* r, double t_min, double t_max, int mat,
@@ -1506,6 +1512,77 @@ int orc_world_render(const orc_world* o, const orc_params* p, const double* cam2
     cam.time0 = cam24[22];
     cam.time1 = cam24[23];
     return render_world(p, &o->w, &cam, v3(bg[0], bg[1], bg[2]), out_mean, stats);
+}
+
+/* ---- caller rays: hit_hittables (hittable.rs:43-55) for rays the caller states ---- */
+
+/* The colour rt_render_features' albedo names for a record (rt_abi.h): what scatter returns as the
+ * attenuation (material.rs:36-87), or a light's emitted value (material.rs:25-34). */
+static V3 record_albedo(const World* w, const HitRecord* rec)
+{
+    const Material* m = &w->materials[rec->mat_handle - 1];
+    switch (m->kind) {
+    case MAT_LAMBERTIAN: case MAT_ISOTROPIC: case MAT_DIFFUSE_LIGHT:
+        return tex_value(&m->tex, rec->u, rec->v, rec->point);
+    case MAT_METAL: return m->albedo;
+    default: return v3(1.0, 1.0, 1.0);                                                    /* material.rs:80 */
+    }
+}
+
+/* One cast per ray, as ray_color makes it (the keyed coordinates set as render_pixel and ray_color
+ * set them), with the caller's interval in place of (0.001, inf). Nothing scatters. */
+static void world_hits(const World* w, uint64_t seed, uint32_t bounce, int64_t n, const orc_ray* rays, orc_hit* out)
+{
+    OrcRng rng;
+    memset(&rng, 0, sizeof rng);
+    rng.seed = seed;
+    rng.render = 1;
+    OrcRng* saved = tl_rng;
+    tl_rng = &rng;
+    for (int64_t i = 0; i < n; ++i) {
+        const orc_ray* q = &rays[i];
+        orc_hit* o = &out[i];
+        memset(o, 0, sizeof *o);
+        rng.pixel = q->key_pixel;
+        rng.sample = q->key_sample;
+        rng.bounce = bounce;
+        Ray r = ray_with_time(v3(q->o[0], q->o[1], q->o[2]), v3(q->d[0], q->d[1], q->d[2]), q->time);
+        HitRecord rec;
+        int top = 0;
+        if (!hit_list_winner(w->hittables, w->n_hittables, &r, q->t_min, q->t_max, &rec, &top)) {
+            o->t = INFINITY;
+            continue;
+        }
+        V3 a = record_albedo(w, &rec);
+        o->t = rec.t;
+        o->p[0] = rec.point.x; o->p[1] = rec.point.y; o->p[2] = rec.point.z;
+        o->n[0] = rec.normal.x; o->n[1] = rec.normal.y; o->n[2] = rec.normal.z;
+        o->albedo[0] = a.x; o->albedo[1] = a.y; o->albedo[2] = a.z;
+        o->hit = 1;
+        o->front_face = rec.front_face;
+        o->mat = rec.mat_handle;
+        o->top = top;
+    }
+    tl_rng = saved;
+}
+
+int orc_world_hit(const orc_world* o, uint64_t seed, uint32_t bounce, int64_t n, const orc_ray* rays, orc_hit* out)
+{
+    if (!o || n < 0 || (n > 0 && (!rays || !out))) return -1;
+    world_hits(&o->w, seed, bounce, n, rays, out);
+    return 0;
+}
+
+int orc_scene_hit(int scene_id, uint64_t scene_seed, const uint8_t* image_rgb, int iw, int ih, uint64_t seed,
+                  uint32_t bounce, int64_t n, const orc_ray* rays, orc_hit* out)
+{
+    if (n < 0 || (n > 0 && (!rays || !out))) return -1;
+    if ((scene_id == 3 || scene_id == 7) && !image_rgb) return -2;
+    World w;
+    if (build_world(&w, scene_id, scene_seed, image_rgb, iw, ih)) return -1;
+    world_hits(&w, seed, bounce, n, rays, out);
+    world_free(&w);
+    return 0;
 }
 
 /* ---- output: Vector3::write_color (math.rs:119-132) and the P3 writer (main.rs:472,591-596) ---- */

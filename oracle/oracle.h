@@ -112,6 +112,29 @@ int orc_world_push(orc_world* w, int id);
 int orc_world_render(const orc_world* w, const orc_params* p, const double* cam24, const double bg[3],
                      double* out_mean, orc_stats* stats);
 
+/* Caller rays: hit_hittables(world.hittables, ray, t_min, t_max) (hittable.rs:43-55) and the
+ * HitRecord it returns, one cast per ray, nothing scattered. Per ray the keyed draw's coordinates
+ * are (seed, key_pixel, key_sample, bounce), as render_pixel and ray_color set them for a cast, so a
+ * constant medium decides as it does for that cast. No validity rules: callers pass valid rays. */
+typedef struct orc_ray {            /* 80 B: rt_ray's layout (rt_abi.h) */
+    double o[3], d[3];              /* origin, direction (not normalised: t is in units of d) */
+    double time, t_min, t_max;
+    uint32_t key_pixel, key_sample;
+} orc_ray;
+typedef struct orc_hit {            /* 96 B; a miss: t = +inf and zeros */
+    double t, p[3], n[3];           /* the record's t, point and normal */
+    double albedo[3];               /* rt_query_out.albedo's colour (rt_abi.h): the texture's value at the
+                                       record's (u, v, p) for Lambertian, Isotropic and DiffuseLight, the
+                                       albedo for Metal, ones for Dielectric */
+    int32_t hit, front_face;
+    int32_t mat;                    /* the record's material handle, 1-based (main.rs:46-49) */
+    int32_t top;                    /* index in world.hittables of the object whose record won */
+} orc_hit;
+int orc_world_hit(const orc_world* w, uint64_t seed, uint32_t bounce, int64_t n, const orc_ray* rays, orc_hit* out);
+/* The same over a built-in scene, built as orc_render and orc_scene_info build it. */
+int orc_scene_hit(int scene_id, uint64_t scene_seed, const uint8_t* image_rgb, int iw, int ih, uint64_t seed,
+                  uint32_t bounce, int64_t n, const orc_ray* rays, orc_hit* out);
+
 /* Output (math.rs:119-132, main.rs:472,591-596). rgb is height x width x 3 f64, row 0 =
  * the bottom image row (y = 0), holding per-pixel sums taken over samples_per_pixel samples;
  * each channel is written as (int)(256 * clamp(sqrt(x * (1.0 / spp)), 0, 0.999)) with Rust's

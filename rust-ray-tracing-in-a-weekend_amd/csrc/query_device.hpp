@@ -52,12 +52,14 @@ __device__ __forceinline__ bool cast_interval(const SceneDev& S, const RayT<R>& 
 {
     best.sub = 0;
     best.side = 0;
-    bool found = false;
+    bool found = false, have = false;   // ANY: a test accepted; CLOSEST: best holds a hit
     (void)found;
+    (void)have;
     auto leaf = [&](int slot, R tmax, HitRefT<R>& b) {
         if constexpr (ANY)
             if (found) return false;
         const rt_prim& p = S.leaf_prims[slot];
+        const HitRefT<R> before = b;   // (CLOSEST: the closest hit so far, once have)
         bool hit = false, done = false;
         if constexpr ((C::F & FEAT_INST) != 0)
             if (p.kind == RT_PRIM_INSTANCE) {
@@ -70,11 +72,22 @@ __device__ __forceinline__ bool cast_interval(const SceneDev& S, const RayT<R>& 
                 done = true;
             }
         if (!done) hit = simple_t<C>(p, r, t_min, tmax, b.t, b.side, cnt, (C::F & FEAT_SHUTTER) != 0);
-        if constexpr (ANY)
+        if constexpr (ANY) {
             if (hit) {
                 found = true;
                 b.t = -(R)RT_INF;
             }
+        } else {
+            // An exact tie (coincident faces: the final scene's ground boxes share their sides; a test
+            // rejects t > t_max only, so both accept). hit_hittables' loop keeps the later entry of the
+            // list; so does this walk, whatever order its structure tests them in: of two top-level
+            // records with the same t the one later in rt_scene_soa.prims stays.
+            if (hit && have && b.t == before.t && S.prim_refs[slot] < S.prim_refs[before.prim]) {
+                b = before;
+                hit = false;
+            }
+            have = have || hit;
+        }
         return hit;
     };
     if (UniformLeaf<C>() && S.tlas_root < 0 && S.tlas_root != RT_DONE) {   // (wave-uniform) a one-leaf top level

@@ -67,6 +67,10 @@ def lib() -> ctypes.CDLL:
         getattr(l, name).restype = I
     l.orc_world_destroy.argtypes = [P]
     l.orc_world_destroy.restype = None
+    l.orc_world_hit.argtypes = [P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int64, P, P]
+    l.orc_world_hit.restype = I
+    l.orc_scene_hit.argtypes = [I, ctypes.c_uint64, P, I, I, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int64, P, P]
+    l.orc_scene_hit.restype = I
     l.orc_write_color.argtypes = [P, I, ctypes.c_int64, P]
     l.orc_write_color.restype = I
     l.orc_write_ppm.argtypes = [P, I, I, I, ctypes.c_char_p]
@@ -158,6 +162,32 @@ def pstream(seed: int, pixel: int, sample: int, n: int) -> np.ndarray:
     return out
 
 
+# orc_ray (rt_ray's layout: the product binding's RAY records pass as they are) and orc_hit
+ORC_RAY = np.dtype([("o", "<f8", (3,)), ("d", "<f8", (3,)), ("time", "<f8"), ("t_min", "<f8"), ("t_max", "<f8"),
+                    ("key_pixel", "<u4"), ("key_sample", "<u4")])
+ORC_HIT = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("n", "<f8", (3,)), ("albedo", "<f8", (3,)), ("hit", "<i4"),
+                    ("front_face", "<i4"), ("mat", "<i4"), ("top", "<i4")])
+assert ORC_RAY.itemsize == 80 and ORC_HIT.itemsize == 96
+
+
+def _ray_records(rays) -> np.ndarray:
+    rays = np.ascontiguousarray(rays)
+    assert rays.dtype.itemsize == 80 and rays.dtype.names == ORC_RAY.names and rays.ndim == 1, rays.dtype
+    return rays
+
+
+def scene_hit(scene_id: int, rays, seed: int = 1, bounce: int = 0, scene_seed: int = 1) -> np.ndarray:
+    """orc_scene_hit: the ORC_HIT records of hit_hittables over a built-in scene for caller rays."""
+    rays = _ray_records(rays)
+    img = earth_texture() if scene_id in (3, 7) else np.zeros((1, 1, 3), np.uint8)
+    out = np.zeros(rays.shape[0], dtype=ORC_HIT)
+    rc = lib().orc_scene_hit(scene_id, scene_seed, img.ctypes.data, img.shape[1], img.shape[0], seed, bounce,
+                             rays.shape[0], rays.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"orc_scene_hit failed: {rc}")
+    return out
+
+
 class OracleWorld:
     """A custom world in the oracle (orc_world_*), built with the calls of the product's
     rtiow_amd.World; TwinWorld below issues every call to both."""
@@ -219,6 +249,15 @@ class OracleWorld:
 
     def push(self, hid):
         self._id(lib().orc_world_push(self.h, hid))
+
+    def hit(self, rays, seed=1, bounce=0) -> np.ndarray:
+        """orc_world_hit: the ORC_HIT records of hit_hittables over this world for caller rays."""
+        rays = _ray_records(rays)
+        out = np.zeros(rays.shape[0], dtype=ORC_HIT)
+        rc = lib().orc_world_hit(self.h, seed, bounce, rays.shape[0], rays.ctypes.data, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"orc_world_hit failed: {rc}")
+        return out
 
     def render(self, cam24, bg, width, height, spp, max_depth=50, render_seed=1, row_begin=0, row_stride=1,
                spp_chunk=0, threads=0):

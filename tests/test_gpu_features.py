@@ -41,9 +41,9 @@ def _spheres_world(rt):
     return tw, ((6.0, 2.0, 5.0), (0.0, 0.5, 0.0), 40.0)
 
 
-def _cornell_world(rt, media: bool):
+def _cornell_world(rt, media: bool, density: float = 0.01):
     """A Cornell-like box seen from far enough that rays pass beside it, with two rotated and
-    translated boxes, or (media) the two boxes as constant media."""
+    translated boxes, or (media) the two boxes as constant media of the given density."""
     tw = fr.LightTwin(rt, 7)
     red = tw.lambertian(tw.solid(0.65, 0.05, 0.05))
     white = tw.lambertian(tw.solid(0.73, 0.73, 0.73))
@@ -60,17 +60,17 @@ def _cornell_world(rt, media: bool):
                       (265.0, 0.0, 295.0))
     b2 = tw.translate(tw.rotate_y(tw.box((0.0, 0.0, 0.0), (165.0, 165.0, 165.0), white), -18.0), (130.0, 0.0, 65.0))
     if media:
-        tw.push(tw.constant_medium(b1, 0.01, tw.isotropic(tw.solid(0.1, 0.1, 0.1))))
-        tw.push(tw.constant_medium(b2, 0.01, tw.isotropic(tw.solid(0.9, 0.9, 0.9))))
+        tw.push(tw.constant_medium(b1, density, tw.isotropic(tw.solid(0.1, 0.1, 0.1))))
+        tw.push(tw.constant_medium(b2, density, tw.isotropic(tw.solid(0.9, 0.9, 0.9))))
     else:
         tw.push(b1)
         tw.push(b2)
     return tw, ((278.0, 278.0, -800.0), (278.0, 278.0, 0.0), 55.0)
 
 
-def _final_world(rt):
-    """Top-level rects, a Perlin sphere, a sphere-bounded medium and a translated, rotated BVH of
-    spheres: the final-scene variant."""
+def _final_world(rt, density: float = 1.5):
+    """Top-level rects, a Perlin sphere, a sphere-bounded medium (of the given density) and a
+    translated, rotated BVH of spheres: the final-scene variant."""
     tw = fr.LightTwin(rt, 11)
     ground = tw.lambertian(tw.solid(0.48, 0.83, 0.53))
     white = tw.lambertian(tw.solid(0.73, 0.73, 0.73))
@@ -79,7 +79,7 @@ def _final_world(rt):
     tw.push(tw.xz_rect(light, -1.0, 1.0, -1.0, 1.0, 4.0))
     tw.push(tw.xy_rect(white, -3.0, 3.0, 0.0, 2.5, -4.0))
     tw.push(tw.sphere(tw.lambertian(tw.noise(4.0)), (-1.6, 0.8, 0.5), 0.8))
-    tw.push(tw.constant_medium(tw.sphere(tw.dielectric(1.5), (1.5, 0.7, 1.0), 0.7), 1.5, tw.isotropic(tw.solid(0.2, 0.4, 0.9))))
+    tw.push(tw.constant_medium(tw.sphere(tw.dielectric(1.5), (1.5, 0.7, 1.0), 0.7), density, tw.isotropic(tw.solid(0.2, 0.4, 0.9))))
     balls = tw.bvh([tw.sphere(white, (0.35 * (i % 5), 0.2 + 0.35 * (i // 5), 0.1 * (i % 3)), 0.15) for i in range(15)])
     tw.push(tw.translate(tw.rotate_y(balls, 15.0), (-0.6, 0.0, -1.8)))
     return tw, ((5.0, 3.0, 8.0), (0.0, 0.8, 0.0), 40.0)
