@@ -101,7 +101,22 @@ void rt_ctx_destroy(rt_ctx* ctx);
 int rt_world_create(uint64_t scene_seed, rt_world** out);
 void rt_world_destroy(rt_world* w);
 
-/* Textures (texture.rs:4-22) -> texture id >= 0. */
+/* Textures (texture.rs:4-22) -> texture id >= 0.
+ * Where the values are the reference's (texture.rs:30-75). The sine under the checker and the noise
+ * (rt_sin, rt_numerics.h) is accurate for |x| < 2^20 * pi / 2 = 1.647e6, and Perlin's lattice index is
+ * an i32 of 64 p at the seventh octave. So at a point p
+ *   - the checker texture is the reference's while |10 * p_i| < 2^20 * pi / 2 on each axis, that is
+ *     |p_i| < 1.647e5;
+ *   - the noise texture is the reference's while |scale * p.z| < 2^20 * pi / 2 and every |p_i| < 2^25
+ *     (from 2^25 the reference itself saturates the cast and then overflows `i + 1`);
+ *   - the image texture has no such limit.
+ * Beyond those limits the values are deterministic (a function of the scene and p alone, the same on
+ * the host and on the device, in renders, feature buffers and rt_trace_rays' albedo) but not the
+ * reference's: a checker cell may take the other colour from |10 p_i| of about 1.6e7, and a noise
+ * value may leave [0, 1] from |scale * p.z| of about 2^40 and is inf or NaN from about 2^120.
+ * tests/test_texture_reference.py and tests/test_gpu_textures.py hold the textures to an independent
+ * high-precision evaluation inside the limits, and the device to the host's bits outside them. The
+ * built-in scenes stay far inside (|p| <= 1000, |scale * p.z| <= 4000). */
 int rt_world_texture_solid(rt_world* w, double r, double g, double b, int* tex_out);
 int rt_world_texture_checker(rt_world* w, const double even[3], const double odd[3], int* tex_out);
 /* Perlin::new() draws from the world's stream (perlin.rs:13-30). */
@@ -1135,7 +1150,9 @@ int rt_pyramid_last_stats(rt_ctx* ctx, rt_pyramid_stats* out);
  *   mat     the material index the record carries (a medium: its phase function); -1 on a miss
  *   flags   RT_HIT_FRONT: the record's front_face; RT_HIT_MEDIUM: the record is a constant medium's
  *   albedo  (rt_query_out.albedo) the colour rt_render_features' albedo names for the record; a
- *           miss: zeros (not a background: a query has none)
+ *           miss: zeros (not a background: a query has none). A caller's rays choose the point a
+ *           texture is taken at: the checker and the noise are the reference's within the limits
+ *           stated at rt_world_texture_*, and deterministic beyond them
  *
  * Any. RT_QUERY_ANY answers "RT_QUERY_CLOSEST with the same ray would report a hit", the medium's
  * keyed draw included: occluded[i] = 1 or 0. The walk stops at the first test that accepts.

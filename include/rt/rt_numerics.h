@@ -244,8 +244,15 @@ RT_HD double rt__kcos(double x, double y)
     return w + (((1.0 - w) - hz) + (z * r - x * y));
 }
 
-/* x = n*pi/2 + (y0 + y1); deterministic for all finite x (accurate to
- * |x| < 2^20*pi/2 — far beyond any argument the path produces). */
+/* x = n*pi/2 + (y0 + y1); deterministic for all finite x, accurate for |x| < 2^20*pi/2 =
+ * 1.647e6: there rt_sin and rt_cos stay within 2 ulp (measured 0.66 and 0.50 against 400-bit
+ * values on the doubles within 3 ulp of every kind of k*pi/2) and every sign is right. The
+ * built-in scenes stay far inside that range; a caller's world need not (a checker at
+ * |10 p| or a noise texture at |scale * p.z| beyond it: rt_abi.h tells callers). Past it the
+ * products fn * pio2_k stop being exact (pio2_1 and pio2_2 carry 31 and 32 significant bits):
+ * the first error over 2 ulp found is rt_cos at |x| = 6.31e6 and rt_sin at 1.262e7, the first
+ * wrong sign of rt_sin and rt_sin_sign at 1.678e7. The results stay within
+ * [-1, 1] to 2^40 and finite to 2^100; from about 2^120 they are inf or NaN. */
 RT_HD int rt__rem_pio2(double x, double* y0, double* y1)
 {
     const double invpio2 = 6.36619772367581382433e-01,
